@@ -9,6 +9,10 @@ inheritance, back-projection + spherical voxel sampling, radius filters,
 BallQuery fuse, clustering, L-shape fit, box rows) over one batch of
 `--frames` synthetic frames per GPU that is resident in HBM, followed for N > 1
 by the all-gather of the box rows.  Prints ONE JSON line on rank 0.
+
+  python bench.py --gpus 1 --steps K --warmup W --dump-outputs DIR
+  also writes the box rows of the last timed step to DIR/rows.npy (float64), for
+  comparing two builds output for output.
 """
 import argparse
 import json
@@ -203,6 +207,26 @@ def parity_block(rows, exp, n_frames, frame_ids):
     return out
 
 
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def dump_outputs(out_dir, rows, limit=DUMP_LIMIT_BYTES, seed=0):
+    """--dump-outputs: what the timed path handed its caller in the last timed step -- the gathered box rows, (n, 18) float64
+    in dist.GATHER_COLUMNS order and in the order the path returns them -- as out_dir/rows.npy.  Above `limit` bytes a fixed,
+    seeded sample of the rows (kept in their order) is written instead, with their positions in rows_sample_index.npy.
+    Returns {file name: shape} for the JSON line."""
+    R = rows.detach().to("cpu", torch.float64).numpy()
+    os.makedirs(out_dir, exist_ok=True)
+    arrays = {"rows": R}
+    if R.nbytes > limit:
+        k = limit // ((R.shape[1] + 1) * 8)          # sampled rows + their float64 index stay under the limit
+        idx = np.sort(np.random.default_rng(seed).choice(R.shape[0], size=k, replace=False))
+        arrays = {"rows": R[idx], "rows_sample_index": idx.astype(np.float64)}
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, name + ".npy"), np.ascontiguousarray(a))
+    return {name + ".npy": list(a.shape) for name, a in arrays.items()}
+
+
 def _cpu_worker(go, barrier, tasks, done):
     """Forked before the GPU is touched; sleeps until the timed GPU region is over, then runs the oracle on one
     frame read from shared memory, together with its siblings (all-cores CPU figure)."""
@@ -367,10 +391,16 @@ def main():
                     help="extra passes AFTER the timed region in which every stage is bracketed with HIP events on the "
                          "launch stream (one stream, one chunk)")
     ap.add_argument("--dump", type=str, default="", help="write the JSON here as well")
+    ap.add_argument("--dump-outputs", type=str, default="", metavar="DIR",
+                    help="after the timed region, write the box rows of the last timed step (what the path returns to its "
+                         "caller) as DIR/rows.npy, float64, at most 64 MB (a seeded sample above that); the inputs are the "
+                         "same from run to run, so two builds can be compared output for output")
     ap.add_argument("--dist-backend", default=None, help="nccl (default on GPUs) | gloo (rehearsal)")
     ap.add_argument("--single-device", action="store_true",
                     help="rehearsal: every rank uses cuda:0 (needs --dist-backend gloo)")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        raise SystemExit("--steps must be at least 1 and --warmup at least 0")
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         sys.exit(spawn_ranks(args.gpus))          # before anything touches the GPU
@@ -516,6 +546,9 @@ def main():
                          device="cpu" if torch.distributed.get_backend() == "gloo" else dev)
         torch.distributed.all_reduce(t, op=torch.distributed.ReduceOp.MAX)
         dt = float(t.item())
+    dumped = None
+    if rank == 0 and args.dump_outputs:             # (the gathered rows are the same on every rank)
+        dumped = dump_outputs(args.dump_outputs, rows)
     n_boxes = int(rows.shape[0])
     if world > 1:                              # every gathered row belongs to a frame of the global batch
         fr = rows[:, 0].long()
@@ -592,6 +625,9 @@ def main():
                        "boxes_per_step_all_ranks": n_boxes, "parallelism": "frames sharded x%d" % world},
             "hbm_copy_GBs_measured": round(copy_rate, 1),
         }
+        if dumped is not None:
+            out["dumped_outputs"] = {"dir": os.path.abspath(args.dump_outputs), "files": dumped,
+                                     "columns": list(D.GATHER_COLUMNS)}
         if pack_ms is not None:
             # `value` is quoted on masks that are resident as packed words (SURVEY.md 8d prices "M/8 mask-bits"); the
             # reference's boundary hands uint8 planes: converting a step's planes, serialised in front of the step

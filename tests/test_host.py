@@ -72,7 +72,20 @@ def test_synthetic_scene_shapes_and_oracle_runs():
 
 def test_reader_pool_fills_shared_staging(tmp_path):
     """dfu3d_amd.reader_pool: forked workers read frames into shared memory at fixed strides; the bytes equal what
-    pipeline.read_frame returns (CPU only: the pool refuses to start once the GPU is initialised)."""
+    pipeline.read_frame returns.  The pool refuses to start once the GPU is initialised, and a GPU test earlier in the same
+    session may have done that: the check runs in a fresh interpreter of its own."""
+    import subprocess
+    import sys
+    repo = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    code = "import sys; sys.path.insert(0, %r); import tests.test_host as t; t._reader_pool_check(%r)" % (repo, str(tmp_path))
+    cmd = [sys.executable] + (["-s"] if sys.flags.no_user_site else []) + ["-c", code]
+    r = subprocess.run(cmd, cwd=repo, capture_output=True, text=True, timeout=300)
+    assert r.returncode == 0, (r.stdout[-2000:], r.stderr[-4000:])
+
+
+def _reader_pool_check(tmp_path):
+    import pathlib
+    tmp_path = pathlib.Path(tmp_path)
     from multiprocessing import shared_memory
     import numpy as np
     from dfu3d_amd import kitti_io, synth
@@ -156,3 +169,25 @@ def test_bench_parity_block_sees_extra_missing_and_moved_rows():
     moved = R.clone(); moved[5, 5 + 8] += 0.01                                   # x of a box by a centimetre
     b = bench.parity_block(moved, exp, 2, frame_ids)
     assert b["rows_equal"] and not b["within_north_star_tolerance"]
+
+
+def test_bench_dump_outputs_writes_the_rows_and_samples_above_the_limit(tmp_path):
+    """bench.py --dump-outputs: the rows as they are (float64, same order) under the size limit; above it a seeded sample that
+    is the same on every call, fits the limit, and whose index file names the rows it kept."""
+    import sys
+    import numpy as np
+    import torch
+    sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), ".."))
+    import bench
+    R = torch.tensor(np.random.default_rng(5).normal(0, 10, (1000, 18)))
+    files = bench.dump_outputs(str(tmp_path / "a"), R)
+    assert files == {"rows.npy": [1000, 18]}
+    got = np.load(tmp_path / "a" / "rows.npy")
+    assert got.dtype == np.float64 and np.array_equal(got, R.numpy())
+    limit = 40 * 19 * 8
+    for d in ("b", "c"):
+        bench.dump_outputs(str(tmp_path / d), R, limit=limit)
+    s, i = np.load(tmp_path / "b" / "rows.npy"), np.load(tmp_path / "b" / "rows_sample_index.npy")
+    assert s.shape == (40, 18) and s.nbytes + i.nbytes <= limit
+    assert np.all(np.diff(i) > 0) and np.array_equal(s, R.numpy()[i.astype(np.int64)])
+    assert np.array_equal(s, np.load(tmp_path / "c" / "rows.npy"))
