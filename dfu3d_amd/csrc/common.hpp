@@ -266,8 +266,13 @@ __device__ __forceinline__ KeyCol load_key_col(const ViewCalib *c, int axis) {
   k.m0 = M[0]; k.m3 = M[3]; k.m6 = M[6]; k.m9 = M[9];
   return k;
 }
-__device__ __forceinline__ double pixel_to_lidar_axis(const ViewCalib &c, const Recip &rc, const KeyCol &kc, int u,
-                                                      int v, float d) {
+// The six scalars of the record the key reads, as a copy a kernel keeps in registers while the record stays in memory;
+// pixel_to_lidar_axis takes either.
+struct KeyCal { float cu, cv, fu, fv, tx, ty; };
+__device__ __forceinline__ KeyCal key_cal(const ViewCalib &c) { return KeyCal{c.cu, c.cv, c.fu, c.fv, c.tx, c.ty}; }
+template <class Cal>
+__device__ __forceinline__ double pixel_to_lidar_axis(const Cal &c, const Recip &rc, const KeyCol &kc, int u, int v,
+                                                      float d) {
   const double dd = (double)d;
   const double xr = div_reused(((double)u - (double)c.cu) * dd, (double)c.fu, rc.rfu) + (double)c.tx;
   const double yr = div_reused(((double)v - (double)c.cv) * dd, (double)c.fv, rc.rfv) + (double)c.ty;

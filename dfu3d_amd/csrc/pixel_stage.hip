@@ -72,6 +72,12 @@ __host__ __device__ inline Table table_view(void *base, int64_t E) {
 }
 static_assert(DFU3D_TABLE_ENTRY_BYTES == 28, "table entry");
 
+// p[i] for a wave-uniform base p and a per-lane index whose byte offset fits in 32 bits: the access compiles to the
+// saddr form (the base in scalar registers, a 32-bit offset per lane) instead of a 64-bit address formed in every lane
+template <class T> __device__ __forceinline__ T &at32(T *p, uint32_t i) {
+  return *(T *)((char *)p + i * (uint32_t)sizeof(T));
+}
+
 // order-preserving key cut to its top (64 - pix_bits) bits | pixel index
 __device__ __forceinline__ unsigned long long combo_word(unsigned long long okey, uint32_t pix,
                                                          int pix_bits) {
@@ -133,14 +139,11 @@ __device__ __forceinline__ double pixel_key(const ViewCalib &c, const Recip &rc,
   return key;
 }
 
-__device__ __forceinline__ void load4(const float *p, int base, int n, float d[PPT]) {
-  if (base + PPT <= n) {
-    const float4 q = *(const float4 *)(p + base);
-    d[0] = q.x; d[1] = q.y; d[2] = q.z; d[3] = q.w;
-  } else {
-#pragma unroll
-    for (int k = 0; k < PPT; k++) d[k] = (base + k < n) ? p[base + k] : 0.0f;
-  }
+// the PPT depths from element i on of the view's map p (wave-uniform): i is a multiple of PPT inside a row, and the rows
+// hold a multiple of PPT pixels (dfu3d_backproject_bin checks W % 4), so the PPT pixels are one float4 of one row
+__device__ __forceinline__ void load4(const float *p, uint32_t i, float d[PPT]) {
+  const float4 q = *(const float4 *)&at32(p, i);
+  d[0] = q.x; d[1] = q.y; d[2] = q.z; d[3] = q.w;
 }
 
 // ---- P1 ---------------------------------------------------------------------
@@ -151,7 +154,7 @@ __device__ __forceinline__ void toggle_first_bit(uint32_t *bitmap_v, int W, int 
   const int row = (int)pix / W, col = (int)pix - row * W;
   const int tile = (row >> 4) * tiles_x + (col >> 6);
   const int local = (row & 15) * TILE_W + (col & 63);
-  atomicXor(&bitmap_v[tile * 32 + (local >> 5)], 1u << (local & 31));
+  atomicXor(&at32(bitmap_v, (uint32_t)(tile * 32 + (local >> 5))), 1u << (local & 31));
 }
 
 // Occupancy of a view's table: one BYTE per SEGMENT of 64 consecutive entries (a line of every plane).  Whoever commits
@@ -253,6 +256,26 @@ inline FastGeom make_fast_geom(const dfu3d_bin_geom &g) {
   return f;
 }
 
+// What tier 1 and the table commits of k_bp_bin read for every pixel, passed by value (17 scalar registers).  The rest of
+// the geometry -- the fp64 fields of dfu3d_bin_geom and FastGeom, read only by tier 1.5 and the table builder -- reaches
+// k_bp_bin through a pointer to a copy in device memory (BinCold), so that it is loaded inside the rare branches that
+// use it and does not sit in scalar registers across the kernel.  (With both records passed by value and the whole
+// calibration record loaded at the entry, k_bp_bin spilled 47 scalar registers through lanes of a vector register.)
+struct HotGeom {
+  float depth_min, r_lo, r_hi, z_max, q_tmin;   // depth_min rounded to float32 as tier 1 compares it
+  float tinv, tc1, pinv, pc1, dmax;
+  int tJ, pJ, t_lo, t_n, p_lo, p_n, mid_ok;
+};
+inline HotGeom make_hot_geom(const dfu3d_bin_geom &g, const FastGeom &fg) {
+  return HotGeom{(float)g.depth_min, fg.r_lo, fg.r_hi, fg.z_max, fg.q_tmin, fg.tinv, fg.tc1, fg.pinv, fg.pc1, fg.dmax,
+                 fg.tJ, fg.pJ, g.t_lo, g.t_n, g.p_lo, g.p_n, fg.mid_ok};
+}
+struct BinCold {
+  dfu3d_bin_geom g;
+  FastGeom fg;
+};
+static_assert(sizeof(BinCold) % 16 == 0, "BinCold: the edge tables behind it stay 16-byte aligned");
+
 // one thread per table entry (tJ + 2 of theta, then pJ + 2 of phi): (E, k) = the edge nearest to the cell's centre and
 // its index, or (NaN, 0)
 __device__ __forceinline__ const double *edge_tab_t(const float2 *tab, const FastGeom &fg) { return (const double *)(tab + fg.tJ + fg.pJ + 4); }
@@ -262,9 +285,10 @@ __device__ __forceinline__ const double *edge_tab_p(const float2 *tab, const Fas
 inline int tables_threads(const FastGeom &fg, const dfu3d_bin_geom &g) {
   return fg.tJ + fg.pJ + 4 + (fg.mid_ok ? g.t_n + g.p_n + 2 : 0);
 }
-__global__ void k_bp_tables(dfu3d_bin_geom g, FastGeom fg, float2 *__restrict__ tab) {
+__global__ void k_bp_tables(dfu3d_bin_geom g, FastGeom fg, float2 *__restrict__ tab, BinCold *__restrict__ cold) {
   const int i = blockIdx.x * blockDim.x + threadIdx.x;
   const double pi = 3.14159265358979323846;
+  if (i == 0 && cold) { cold->g = g; cold->fg = fg; }      // (k_bp_bin's copy of the records)
   if (i >= fg.tJ + fg.pJ + 4) {
     // tier 1.5 (pixel_bin_mid): edge k of the window in the space the fp64 test works in -- -cos(B) for theta,
     // tan(B) for phi (B = rmin + k * vsize as the reference's floor((angle - rmin) / vsize) implies it)
@@ -395,7 +419,7 @@ __device__ __forceinline__ void backproject_f32(const FastCal &fc, int col, int 
 // compiler interleaves their transcendental and table latencies and pairs their float32 arithmetic): res[k] = NOBIN
 // (certainly not binned), AMBIG (tier 2 decides) or the table index, with it / ip the window coordinates of the bin.
 template <int N>
-__device__ __forceinline__ void classify_fast(const FastCal &fc, const dfu3d_bin_geom &g, const FastGeom &fg,
+__device__ __forceinline__ void classify_fast(const FastCal &fc, const HotGeom &fg,
                                               const float2 *__restrict__ tab, int row, const int (&col)[N],
                                               const float (&d)[N], uint32_t (&res)[N], int (&it)[N], int (&ip)[N]) {
   float xf[N], yf[N], zf[N], err[N];
@@ -404,7 +428,7 @@ __device__ __forceinline__ void classify_fast(const FastCal &fc, const dfu3d_bin
 #pragma unroll
   for (int k = 0; k < N; k++) {
     backproject_f32(fc, col[k], row, d[k], xf[k], yf[k], zf[k], err[k]);
-    const bool dok = (d[k] >= (float)g.depth_min) && (d[k] > 0.0f);      // my_loader.py:507-509
+    const bool dok = (d[k] >= fg.depth_min) && (d[k] > 0.0f);      // my_loader.py:507-509
     dead[k] = !dok || (zf[k] > fg.z_max + err[k]);                       // certainly z >= z_max (my_loader.py:540)
     any_live = any_live || !dead[k];
     res[k] = NOBIN; it[k] = 0; ip[k] = 0;
@@ -439,26 +463,25 @@ __device__ __forceinline__ void classify_fast(const FastCal &fc, const dfu3d_bin
     const float dp = 1.5e-6f + 1.1f * turn * __builtin_amdgcn_rsqf(s2);  // (s2 > 1e-4 or not ok); dp >= dq
     ok = ok & tab_bin(tab + fg.tJ + 2, fg.pinv, fg.pc1, fg.pJ, qp, dp, kp);
     ok = ok & (dp < fg.dmax);
-    const uint32_t itk = kt - (uint32_t)g.t_lo, ipk = kp - (uint32_t)g.p_lo;      // (wraps for a bin below the window)
-    ok = ok & (itk < (uint32_t)g.t_n) & (ipk < (uint32_t)g.p_n);
+    const uint32_t itk = kt - (uint32_t)fg.t_lo, ipk = kp - (uint32_t)fg.p_lo;      // (wraps for a bin below the window)
+    ok = ok & (itk < (uint32_t)fg.t_n) & (ipk < (uint32_t)fg.p_n);
     it[k] = (int)itk;                                                    // (meaningful only for a decided, binned pixel)
     ip[k] = (int)ipk;
     // (a 24-bit multiply: v_mul_lo_u32 / v_mad_u64_u32 issue at a quarter of the rate; make_fast_geom switches tier 1 off
     // for a window of 2^24 or more bins along an axis)
-    res[k] = (dead[k] | th_out) ? NOBIN : (ok ? __umul24(itk, (uint32_t)g.p_n) + ipk : AMBIG);
+    res[k] = (dead[k] | th_out) ? NOBIN : (ok ? __umul24(itk, (uint32_t)fg.p_n) + ipk : AMBIG);
   }
 }
 
 __device__ __forceinline__ uint32_t pixel_bin_fast(const ViewCalib &c, const Recip &rc, const FastCal &fc,
-                                                   const dfu3d_bin_geom &g, const FastGeom &fg,
-                                                   const float2 *__restrict__ tab,
+                                                   const HotGeom &hg, const float2 *__restrict__ tab,
                                                    int row, int col, float d, const KeyCol &kc, bool want_key,
                                                    double &key, int &it_out, int &ip_out) {
   const int cols[1] = {col};
   const float ds[1] = {d};
   uint32_t res[1];
   int it[1], ip[1];
-  classify_fast<1>(fc, g, fg, tab, row, cols, ds, res, it, ip);
+  classify_fast<1>(fc, hg, tab, row, cols, ds, res, it, ip);
   it_out = it[0];
   ip_out = ip[0];
   if (want_key && res[0] < AMBIG) {
@@ -537,13 +560,13 @@ constexpr int P1_OCC = 7;                          // workgroups per compute uni
                                                    // (budgets for 6 / 8 spilled: 3.98 / 6.11 ms against 3.23).  Round 4: a kept pixel carries 16 bits
                                                    // + 16 bits of window coordinates across the barrier and nothing else (its depth is read again, its
                                                    // key formed behind the barrier): 67 registers, seven waves per SIMD -- 2.85 -> 2.61 ms (six: 2.75;
-                                                   // eight, with 12 B of scratch: 2.64)
+                                                   // eight, with 12 B of scratch: 2.64).  After the uniform-state diet: 65 registers and 94 SGPRs,
+                                                   // still over eight's 64 / 80
 constexpr int RPT = 2;                             // rows per thread: a workgroup's tile is TILE_W x (RPT * TILE_H) pixels --
                                                    // the window set-up, its flush and the reductions are paid once per 2048 pixels
 __global__ __launch_bounds__(PB, P1_OCC) void k_bp_bin(
     const float *__restrict__ depth, const ViewCalib *__restrict__ calib,
-    const FastCal *__restrict__ fastcal, const float2 *__restrict__ tab, dfu3d_bin_geom g, FastGeom fg, int W, int H,
-    int tiles_x, int tiles_y, int key_axis,
+    const FastCal *__restrict__ fastcal, const float2 *__restrict__ tab, HotGeom hg, int W, int H, int tiles_x, int tiles_y, int key_axis,
     int64_t E_view, void *table, int64_t E_total, int *__restrict__ n_amb, uint32_t *__restrict__ amb_list,
     int pix_bits, uint32_t *__restrict__ bitmap, int BW, uint8_t *__restrict__ occ, int OW) {
   __shared__ uint32_t s_bits[32 * RPT];           // this workgroup's piece of the first-pixel bit map (RPT bit-map tiles)
@@ -557,12 +580,19 @@ __global__ __launch_bounds__(PB, P1_OCC) void k_bp_bin(
   DBG_T_COUNT(8);
   const int v = blockIdx.y;
   const int HW = H * W;
-  const ViewCalib c = calib[v];
+  // The calibration record stays in memory: the exact key reads ten of its scalars (kcal, kcol: loaded behind the origin's
+  // barrier, where the keys are formed), tier 1.5 the rest, inside its own branch.
+  const ViewCalib &c = calib[v];
   const FastCal fc = fastcal[v];
-  const Recip rc = recip_of(fc);
-  const KeyCol kcol = load_key_col(calib + v, key_axis);
+  const BinCold *cold = (const BinCold *)tab - 1;  // (the scratch holds the records right in front of the edge tables)
+  // the view's planes of the table, its depth map and its list of undecided pixels as wave-uniform bases: every access
+  // below is one of these plus a 32-bit offset per lane (at32; dfu3d_backproject_bin keeps a view's table below 2^29 entries)
   const Table T = table_view(table, E_total);
   const int64_t tb0 = (int64_t)v * E_view;
+  uint32_t *const cnt_v = T.cnt + tb0, *const first_v = T.first + tb0;
+  unsigned long long *const kmin_v = T.kmin + tb0, *const combo_v = T.combo + tb0;
+  const float *const depth_v = depth + (size_t)v * HW;
+  uint32_t *const amb_v = amb_list + (size_t)v * HW;
   const int ty = blockIdx.x / tiles_x, tx = blockIdx.x - ty * tiles_x;     // ty counts RPT bit-map tile rows
   // (workgroup order, measured with tools/ab_builds.py: tiles column by column 2.60 ms against 2.57; the same tile of consecutive
   // views side by side -- no two workgroups in flight on one table -- 2.89: the table atomics live on lines their neighbours
@@ -574,7 +604,10 @@ __global__ __launch_bounds__(PB, P1_OCC) void k_bp_bin(
   const int row0 = ty * (RPT * TILE_H) + trow;
   const int col = tx * TILE_W + (threadIdx.x & 15) * PPT;
   if (threadIdx.x == 0) { s_namb = 0; s_t0 = 0x7FFFFFFF; s_p0 = 0x7FFFFFFF; }
-  if (threadIdx.x < 32 * RPT) s_bits[threadIdx.x] = 0u;
+  // the workgroup's bit-map words belong to its first wave: a wave-uniform branch, not a lane mask kept across the kernel
+  static_assert(32 * RPT == DFU3D_WAVE, "one bit-map word per lane of wave 0");
+  const bool wave0 = __builtin_amdgcn_readfirstlane(threadIdx.x) < DFU3D_WAVE;
+  if (wave0) s_bits[threadIdx.x] = 0u;
   uint32_t *bitmap_v = bitmap + (size_t)v * BW;
   uint8_t *occ_v = occ + (size_t)v * OW * 4;
   // The window keeps a bin's first pixel as its index INSIDE the workgroup's tile (row-major over the tile's
@@ -587,7 +620,12 @@ __global__ __launch_bounds__(PB, P1_OCC) void k_bp_bin(
   const uint32_t pix00 = (uint32_t)(ty * (RPT * TILE_H) * W + tx * TILE_W);        // the tile's first pixel
   auto global_pix = [&](uint32_t loc) { return pix00 + __umul24(loc >> 6, (uint32_t)W) + (loc & 63u); };
   static_assert(TILE_W == 64, "tile-local pixel index");
-  for (int i = threadIdx.x; i < WIN_T * WIN_P; i += PB) { s_kmin[i] = ~0ull; s_combo[i] = ~0ull; s_cnt[i] = 0u; s_first[i] = NOBIN; }
+  static_assert(WIN_T * WIN_P % PB == 0, "window reset and flush: every thread takes the same number of slots");
+#pragma unroll
+  for (int j = 0; j < WIN_T * WIN_P / PB; j++) {
+    const int i = threadIdx.x + j * PB;
+    s_kmin[i] = ~0ull; s_combo[i] = ~0ull; s_cnt[i] = 0u; s_first[i] = NOBIN;
+  }
   __syncthreads();
   DBG_T(0);                                        // set-up: records, window reset, barrier
   // what a kept pixel carries across the origin's barrier: its window coordinates in ONE word (theta | phi << 16; NOBIN: not
@@ -605,15 +643,14 @@ __global__ __launch_bounds__(PB, P1_OCC) void k_bp_bin(
 #pragma unroll
     for (int k = 0; k < PPT; k++) tp[r][k] = NOBIN;
     if (!inside[r]) continue;
-    const float *dv = depth + (size_t)v * HW;
     float d[PPT];
-    load4(dv + (size_t)row * W, col, W, d);          // (columns past the image come back as depth 0: not binned)
+    load4(depth_v, __umul24((uint32_t)row, (uint32_t)W) + (uint32_t)col, d);
     int cols[PPT];
 #pragma unroll
     for (int k = 0; k < PPT; k++) cols[k] = col + k;
     uint32_t res[PPT];
     int its[PPT], ips[PPT];
-    classify_fast<PPT>(fc, g, fg, tab, row, cols, d, res, its, ips);
+    classify_fast<PPT>(fc, hg, tab, row, cols, d, res, its, ips);
 #pragma unroll
     for (int k = 0; k < PPT; k++) {
       const uint32_t b = res[k];
@@ -633,7 +670,7 @@ __global__ __launch_bounds__(PB, P1_OCC) void k_bp_bin(
       amb_mask &= amb_mask - 1u;
       const uint32_t pix = (uint32_t)((row0 + (bit / PPT) * TILE_H) * W + col + (bit % PPT));
       if (slot < P1_AMB) s_amb[slot] = pix;
-      else amb_list[(size_t)v * HW + atomicAdd(&n_amb[v], 1)] = pix;
+      else at32(amb_v, (uint32_t)atomicAdd(&n_amb[v], 1)) = pix;
       slot++;
     }
   }
@@ -645,6 +682,9 @@ __global__ __launch_bounds__(PB, P1_OCC) void k_bp_bin(
   if (lane_id() == 0 && tmin != 0x7FFFFFFF) { atomicMin(&s_t0, tmin); atomicMin(&s_p0, pmin); }
   __syncthreads();
   const int t0 = s_t0, p0 = s_p0;
+  const KeyCal kcal = key_cal(c);
+  const Recip rc = recip_of(fc);
+  const KeyCol kcol = load_key_col(calib + v, key_axis);
   DBG_T(2);                                        // origin reduction + barrier (= waiting for the slowest wave's classification)
   // every kept pixel goes to the LDS window on its own.  (Round 2 merged the runs of equal bins among a thread's four
   // consecutive pixels first: fewer LDS atomics, but the bookkeeping of the runs took more vector instructions than the
@@ -652,15 +692,16 @@ __global__ __launch_bounds__(PB, P1_OCC) void k_bp_bin(
 #pragma unroll
   for (int r = 0; r < RPT; r++) {
     if (!inside[r]) continue;
-    const uint32_t base = (uint32_t)((row0 + r * TILE_H) * W + col);
+    const uint32_t ro = __umul24((uint32_t)(row0 + r * TILE_H), (uint32_t)W);
+    const uint32_t base = ro + (uint32_t)col;
     float dk[PPT];                                   // (the row's depths once more: a hit in the cache, eight registers less across the barrier)
-    load4(depth + (size_t)v * HW + (size_t)(row0 + r * TILE_H) * W, col, W, dk);
+    load4(depth_v, base, dk);
     const uint32_t loc0 = (uint32_t)((trow + r * TILE_H) * TILE_W + (threadIdx.x & 15) * PPT);
 #pragma unroll
     for (int k = 0; k < PPT; k++) {
       if (tp[r][k] == NOBIN) continue;
       const uint32_t it_k = tp[r][k] & 0xFFFFu, ip_k = tp[r][k] >> 16;
-      double key = pixel_to_lidar_axis(c, rc, kcol, col + k, row0 + r * TILE_H, dk[k]);
+      double key = pixel_to_lidar_axis(kcal, rc, kcol, col + k, row0 + r * TILE_H, dk[k]);
       key += 0.0;                                                 // -0.0 -> +0.0, every other value unchanged
       const unsigned long long ok = ordered_key(key);
       const unsigned long long cm = combo_word(ok, base + k, pix_bits);
@@ -672,12 +713,11 @@ __global__ __launch_bounds__(PB, P1_OCC) void k_bp_bin(
         atomicMin(&s_kmin[w], ok);
         atomicMin(&s_combo[w], cm);
       } else {                                                    // outside the window: direct
-        const uint32_t b = __umul24(it_k, (uint32_t)g.p_n) + ip_k;
-        const int64_t e = tb0 + b;
-        atomicAdd(&T.cnt[e], 1u);
-        const uint32_t oldf = atomicMin(&T.first[e], base + k);
-        atomicMin(&T.kmin[e], ok);
-        atomicMin(&T.combo[e], cm);
+        const uint32_t b = __umul24(it_k, (uint32_t)hg.p_n) + ip_k;
+        atomicAdd(&at32(cnt_v, b), 1u);
+        const uint32_t oldf = atomicMin(&at32(first_v, b), base + k);
+        atomicMin(&at32(kmin_v, b), ok);
+        atomicMin(&at32(combo_v, b), cm);
         mark_segment(occ_v, b);
         if (oldf > base + k) new_first(loc0 + k, oldf);
       }
@@ -695,7 +735,7 @@ __global__ __launch_bounds__(PB, P1_OCC) void k_bp_bin(
       bool decided = false;
       MidOut mo;
       uint32_t b = NOBIN;
-      if (fg.mid_ok) b = pixel_bin_mid(c, rc, g, fg, tab, W, (int)pix, depth[(size_t)v * HW + pix], decided, &mo);
+      if (hg.mid_ok) b = pixel_bin_mid(c, rc, cold->g, cold->fg, tab, W, (int)pix, at32(depth_v, pix), decided, &mo);
       if (!decided) continue;
       s_amb[i] = NOBIN;                                           // done
       if (b == NOBIN) continue;                                   // certainly not binned
@@ -713,11 +753,10 @@ __global__ __launch_bounds__(PB, P1_OCC) void k_bp_bin(
         atomicMin(&s_kmin[w], ok);
         atomicMin(&s_combo[w], cm);
       } else {
-        const int64_t e = tb0 + b;
-        atomicAdd(&T.cnt[e], 1u);
-        const uint32_t oldf = atomicMin(&T.first[e], pix);
-        atomicMin(&T.kmin[e], ok);
-        atomicMin(&T.combo[e], cm);
+        atomicAdd(&at32(cnt_v, b), 1u);
+        const uint32_t oldf = atomicMin(&at32(first_v, b), pix);
+        atomicMin(&at32(kmin_v, b), ok);
+        atomicMin(&at32(combo_v, b), cm);
         mark_segment(occ_v, b);
         if (oldf > pix) new_first(loc, oldf);
       }
@@ -729,25 +768,24 @@ __global__ __launch_bounds__(PB, P1_OCC) void k_bp_bin(
   // flush the window: one set of global atomics per touched bin.  The atomic on `first` returns the value it replaced
   // (the bit-map update below needs it): all of a thread's atomics are issued before the first returned value is looked
   // at -- one memory round trip per workgroup instead of one per slot of the thread.
-  constexpr int FL = (WIN_T * WIN_P + PB - 1) / PB;
+  constexpr int FL = WIN_T * WIN_P / PB;
   uint32_t f_loc[FL], f_new[FL], f_old[FL], f_seg[FL];
 #pragma unroll
   for (int i = 0; i < FL; i++) {
     const int w = threadIdx.x + i * PB;
     f_loc[i] = 0u; f_new[i] = NOBIN; f_old[i] = 0u; f_seg[i] = NOBIN;
-    const uint32_t cw = (w < WIN_T * WIN_P) ? s_cnt[w] : 0u;
+    const uint32_t cw = s_cnt[w];
     if (cw == 0u) continue;
     static_assert(WIN_T * WIN_P <= 768 && WIN_P == 48, "w / 48 as (w * 1366) >> 16 is exact below 768 * 48 / 18");
     const uint32_t wq = __umul24((uint32_t)w, 1366u) >> 16, wr = (uint32_t)w - __umul24(wq, (uint32_t)WIN_P);   // w / 48, w % 48
-    const uint32_t b = __umul24((uint32_t)t0 + wq, (uint32_t)g.p_n) + ((uint32_t)p0 + wr);
-    const int64_t e = tb0 + b;
+    const uint32_t b = __umul24((uint32_t)t0 + wq, (uint32_t)hg.p_n) + ((uint32_t)p0 + wr);
     f_seg[i] = b >> SEG_SHIFT;
     f_loc[i] = s_first[w];
     f_new[i] = global_pix(f_loc[i]);
-    atomicAdd(&T.cnt[e], cw);
-    f_old[i] = atomicMin(&T.first[e], f_new[i]);
-    atomicMin(&T.kmin[e], s_kmin[w]);
-    atomicMin(&T.combo[e], s_combo[w]);
+    atomicAdd(&at32(cnt_v, b), cw);
+    f_old[i] = atomicMin(&at32(first_v, b), f_new[i]);
+    atomicMin(&at32(kmin_v, b), s_kmin[w]);
+    atomicMin(&at32(combo_v, b), s_combo[w]);
   }
 #pragma unroll
   for (int i = 0; i < FL; i++)
@@ -760,15 +798,15 @@ __global__ __launch_bounds__(PB, P1_OCC) void k_bp_bin(
   DBG_T(6);                                        // barrier
   // the workgroup's own bits: contiguous 128-byte wave atomics, one per bit-map tile (XOR: other tiles may already
   // have toggled here)
-  if (threadIdx.x < 32 * RPT && s_bits[threadIdx.x]) {
+  if (wave0 && s_bits[threadIdx.x]) {
     const int sub = threadIdx.x >> 5;                             // which of the RPT bit-map tiles
     if (ty * RPT + sub < tiles_y)
-      atomicXor(&bitmap_v[((size_t)(ty * RPT + sub) * tiles_x + tx) * 32 + (threadIdx.x & 31)], s_bits[threadIdx.x]);
+      atomicXor(&at32(bitmap_v, (uint32_t)(((ty * RPT + sub) * tiles_x + tx) * 32) + (threadIdx.x & 31)), s_bits[threadIdx.x]);
   }
   const int na = min(s_namb, P1_AMB);
   DBG_T(7);                                        // bit-map flush
   for (int i = threadIdx.x; i < na; i += PB)      // (what the middle tier left: in practice nothing)
-    if (s_amb[i] != NOBIN) amb_list[(size_t)v * HW + atomicAdd(&n_amb[v], 1)] = s_amb[i];
+    if (s_amb[i] != NOBIN) at32(amb_v, (uint32_t)atomicAdd(&n_amb[v], 1)) = s_amb[i];
 }
 
 
@@ -1160,8 +1198,8 @@ __global__ void k_bp_finalize(int V, int max_voxels, int cap_vox, int *__restric
 // out[0] pixels tried, out[1] undecided by tier 1, out[2] DISAGREEMENTS among the decided (bin, or the key of a kept
 // pixel), out[3] pixels tier 1 kept.  Depths in [d_lo, d_hi), every fourth one 50x closer.
 __global__ void k_selftest_classify(const ViewCalib *__restrict__ calib, const FastCal *__restrict__ fastcal,
-                                    const float2 *__restrict__ tab, dfu3d_bin_geom g, FastGeom fg, int H, int W,
-                                    int key_axis, long long n, unsigned long long seed, double d_lo, double d_hi,
+                                    const float2 *__restrict__ tab, dfu3d_bin_geom g, FastGeom fg, HotGeom hg, int H,
+                                    int W, int key_axis, long long n, unsigned long long seed, double d_lo, double d_hi,
                                     unsigned long long *out) {
   const ViewCalib c = calib[0];
   const FastCal fc = fastcal[0];
@@ -1179,7 +1217,7 @@ __global__ void k_selftest_classify(const ViewCalib *__restrict__ calib, const F
     double k1 = 0.0, k2 = 0.0;
     int it_, ip_;
     bool rerr = false;
-    const uint32_t b1 = pixel_bin_fast(c, rc, fc, g, fg, tab, row, col, d, kcol, true, k1, it_, ip_);
+    const uint32_t b1 = pixel_bin_fast(c, rc, fc, hg, tab, row, col, d, kcol, true, k1, it_, ip_);
     const uint32_t b2 = pixel_bin(c, rc, g, W, row * W + col, d, key_axis, k2, rerr);
     tried++;
     if (b1 == AMBIG) {                              // tier 1.5 takes it in P4: a decision of its own must be pixel_bin's
@@ -1249,10 +1287,11 @@ extern "C" int dfu3d_selftest_classify(const float *calib, int32_t H, int32_t W,
   if (hipMemsetAsync(out4, 0, 32, st) != hipSuccess) return DFU3D_ELAUNCH;
   hipLaunchKernelGGL(k_bp_prep, dim3(1), dim3(64), 0, st, (const ViewCalib *)calib, 1, H, W, fastcal);
   DFU3D_LAUNCH_CHECK();
-  hipLaunchKernelGGL(k_bp_tables, dim3((tables_threads(fg, *geom) + 255) / 256), dim3(256), 0, st, *geom, fg, tab);
+  hipLaunchKernelGGL(k_bp_tables, dim3((tables_threads(fg, *geom) + 255) / 256), dim3(256), 0, st, *geom, fg, tab,
+                     (BinCold *)nullptr);
   DFU3D_LAUNCH_CHECK();
   hipLaunchKernelGGL(k_selftest_classify, dim3(2048), dim3(256), 0, st, (const ViewCalib *)calib, fastcal, tab,
-                     *geom, fg, H, W, key_axis, (long long)n, (unsigned long long)seed, d_lo, d_hi,
+                     *geom, fg, make_hot_geom(*geom, fg), H, W, key_axis, (long long)n, (unsigned long long)seed, d_lo, d_hi,
                      (unsigned long long *)out4);
   DFU3D_LAUNCH_CHECK();
   return DFU3D_OK;
@@ -1307,7 +1346,7 @@ extern "C" int dfu3d_bin_table_init(void *table, int64_t E, void *stream) {
 // Scratch carve-up.
 // blk_cnt (int32 words): n_amb[V], n_q[V], q_cursor[V], n_occ[V], bitmap[V*BW], occ[V*OW] -- everything up to here is
 //   zeroed at the start of a pass --, wpre[V*NJ], seg_list[V*NSEG], q_cnt[V*cap_q], q_bins[V*cap_q], q_rank[V*cap_q], the float32
-//   calibration constants (80 B per view) and the edge tables of tier 1 (8 B x (TAB_T_MAX + TAB_P_MAX + 4) at most; the carve-up keeps round 2's 16 B)
+//   calibration constants (80 B per view), k_bp_bin's copy of the geometry records (BinCold, 208 B) and the edge tables of tier 1 (8 B x (TAB_T_MAX + TAB_P_MAX + 4) at most; the carve-up keeps round 2's 16 B)
 //   (BW = 32 words per 64x16 tile, NJ = H * tiles_x, NSEG = 64-entry segments of a view's table, OW = NSEG / 4 words of
 //   occupancy bytes, cap_q: queue_cap)
 // pix_bin (uint32 words): [0, V*HW) bin id per pixel (written only for views under repair),
@@ -1331,7 +1370,7 @@ extern "C" int64_t dfu3d_backproject_scratch_words(int32_t V, int32_t H, int32_t
   const int64_t cap_q = queue_cap(HW, max_points, cap_vox);
   if (pix_words) *pix_words = 2 * V * HW;
   const int64_t NSEG = table_segments(table_entries), OW = (NSEG + 3) / 4;
-  if (blk_words) *blk_words = 4 * (int64_t)V + V * BW + V * OW + V * NJ + V * NSEG + 3 * V * cap_q + 20 * (int64_t)V + 16 +
+  if (blk_words) *blk_words = 4 * (int64_t)V + V * BW + V * OW + V * NJ + V * NSEG + 3 * V * cap_q + 20 * (int64_t)V + (int64_t)(sizeof(BinCold) / 4) + 16 +
                               4 * (int64_t)(TAB_T_MAX + TAB_P_MAX) + 16;
   return 0;
 }
@@ -1361,6 +1400,7 @@ extern "C" int dfu3d_backproject_bin(
   const int BW = tiles_x * tiles_y * 32, NJ = H * tiles_x;
   const int cap_q = queue_cap(HW64, geom->max_points_per_voxel, cap_vox);
   const int64_t E_view = (int64_t)geom->t_n * geom->p_n;
+  if (E_view >= (1ll << 29)) return DFU3D_ERANGE;    // k_bp_bin addresses a view's 8-byte planes with 32-bit byte offsets
   const int64_t E_total = E_view * V;
   hipStream_t st = (hipStream_t)stream;
   const int NSEG = (int)table_segments(E_view), OW = (NSEG + 3) / 4;       // OW: words of the occupancy bytes
@@ -1376,7 +1416,8 @@ extern "C" int dfu3d_backproject_bin(
   uint32_t *q_bins = (uint32_t *)(q_cnt + (size_t)V * cap_q);
   int *q_rank = (int *)(q_bins + (size_t)V * cap_q);
   FastCal *fastcal = (FastCal *)(((uintptr_t)(q_rank + (size_t)V * cap_q) + 15) & ~(uintptr_t)15);   // 80 B per view
-  const float2 *tab = (const float2 *)(fastcal + V);                  // edge tables of tier 1: (tJ + pJ + 4) x 8 B
+  BinCold *cold = (BinCold *)(fastcal + V);                           // written by k_bp_tables
+  const float2 *tab = (const float2 *)(cold + 1);                     // edge tables of tier 1: (tJ + pJ + 4) x 8 B
   const FastGeom fg = make_fast_geom(*geom);
   int pix_bits = 1;
   while ((1ll << pix_bits) < HW64) pix_bits++;
@@ -1389,10 +1430,10 @@ extern "C" int dfu3d_backproject_bin(
     if (dfu3d_fill_async(blk_cnt, 0, sizeof(int) * (4 * (size_t)V + (size_t)V * BW + (size_t)V * OW), st) != hipSuccess) return DFU3D_ELAUNCH;
     hipLaunchKernelGGL(k_bp_prep, dim3((V + 63) / 64), dim3(64), 0, st, cal, V, H, W, fastcal);
     DFU3D_LAUNCH_CHECK();
-    hipLaunchKernelGGL(k_bp_tables, dim3((tables_threads(fg, *geom) + 255) / 256), dim3(256), 0, st, *geom, fg, (float2 *)tab);
+    hipLaunchKernelGGL(k_bp_tables, dim3((tables_threads(fg, *geom) + 255) / 256), dim3(256), 0, st, *geom, fg, (float2 *)tab, cold);
     DFU3D_LAUNCH_CHECK();
-    hipLaunchKernelGGL(k_bp_bin, dim3(tiles_x * ((tiles_y + RPT - 1) / RPT), V), dim3(PB), 0, st, depth, cal, fastcal, tab, *geom,
-                       fg, W, H, tiles_x, tiles_y, key_axis, E_view, table, E_total, n_amb, q_list, pix_bits,
+    hipLaunchKernelGGL(k_bp_bin, dim3(tiles_x * ((tiles_y + RPT - 1) / RPT), V), dim3(PB), 0, st, depth, cal, fastcal, tab,
+                       make_hot_geom(*geom, fg), W, H, tiles_x, tiles_y, key_axis, E_view, table, E_total, n_amb, q_list, pix_bits,
                        bitmap, BW, (uint8_t *)occ, OW);
     DFU3D_LAUNCH_CHECK();
   }

@@ -5,7 +5,7 @@ assembly hipcc emits with the product's flags.
 
 Per kernel: vector / scalar / LDS / global-memory instruction counts of the whole body (static: both sides of every branch
 count), the fp64 and transcendental share of the vector instructions, VGPRs, SGPRs, LDS bytes, scratch bytes and the waves
-per SIMD the VGPR count allows (512 VGPRs per SIMD lane).  Used to check a change before it is sent to the GPU box:
+per SIMD the VGPR count allows (512 VGPRs per SIMD lane), and the spilled SGPRs / VGPRs the code object reports.  Used to check a change before it is sent to the GPU box:
 scratch must stay 0, the VGPR count decides the occupancy."""
 import os
 import re
@@ -63,8 +63,9 @@ def main():
     src = sys.argv[1]
     want = sys.argv[2:]
     text = assembly(src)
-    print("%-44s %6s %6s %6s %5s %5s %5s %5s %5s %6s %7s %6s" % ("kernel", "VALU", "f64", "trans", "SALU", "LDS", "vmem", "VGPR",
-                                                                "SGPR", "waves", "LDS B", "scratch"))
+    print("%-44s %6s %6s %6s %5s %5s %5s %5s %5s %6s %7s %6s %11s %11s" % ("kernel", "VALU", "f64", "trans", "SALU", "LDS", "vmem",
+                                                                            "VGPR", "SGPR", "waves", "LDS B", "scratch",
+                                                                            "sgpr_spill", "vgpr_spill"))
     for name, (body, block) in sorted(kernels(text).items()):
         short = re.sub(r"\(.*", "", demangle(name)).replace("(anonymous namespace)::", "").replace("void ", "")
         if want and not any(w in short for w in want):
@@ -74,11 +75,12 @@ def main():
         f64 = [i for i in valu if "_f64" in i]
         trans = [i for i in valu if re.match(r"v_(rcp|rsq|sqrt|exp|log|sin|cos)_", i)]
         vg = field(block, "vgpr_count")
-        print("%-44s %6d %6d %6d %5d %5d %5d %5d %5d %6d %7d %6d" % (
+        print("%-44s %6d %6d %6d %5d %5d %5d %5d %5d %6d %7d %6d %11d %11d" % (
             short[:44], len(valu), len(f64), len(trans), sum(i.startswith("s_") for i in ins),
             sum(i.startswith("ds_") for i in ins), sum(i.startswith(("global_", "buffer_", "flat_", "scratch_")) for i in ins),
             vg, field(block, "sgpr_count"), min(8, 512 // max(vg, 1)) if vg > 0 else -1,
-            field(block, "group_segment_fixed_size"), field(block, "private_segment_fixed_size")))
+            field(block, "group_segment_fixed_size"), field(block, "private_segment_fixed_size"),
+            field(block, "sgpr_spill_count"), field(block, "vgpr_spill_count")))
 
 
 if __name__ == "__main__":
