@@ -8,11 +8,17 @@ A step = one pass of the whole hot path (FOV filter, plane RANSAC, label
 inheritance, back-projection + spherical voxel sampling, radius filters,
 BallQuery fuse, clustering, L-shape fit, box rows) over one batch of
 `--frames` synthetic frames per GPU that is resident in HBM, followed for N > 1
-by the all-gather of the box rows.  Prints ONE JSON line on rank 0.
+by the all-gather of the box rows.  Prints ONE JSON line on rank 0.  A plain run
+does only what that line's `value` needs: set up, warm up, time the steps, print.
 
   python bench.py --gpus 1 --steps K --warmup W --dump-outputs DIR
   also writes the box rows of the last timed step to DIR/rows.npy (float64), for
   comparing two builds output for output.
+
+  python bench.py --full
+  also measures and checks everything else, after the timed region: the kernel
+  table, roofline and big-pool radius-filter passes, the measured copy rate, the
+  mask-packing cost, the CPU baselines and the `parity` block against the oracle.
 """
 import argparse
 import json
@@ -362,8 +368,8 @@ def main():
                     help="concurrent HIP streams, one chunk each.  Default: 2 streams x 32-frame chunks, the engine's throughput "
                          "configuration (stages of different chunks overlap; measured in round 3 against 4 x 16, 1 x 64, 4 x 32, "
                          "2 x 16, 4 x 8: 2 x 32 is 1-3 %% ahead of 4 x 16 and 6 %% ahead of one stream).  The kernel table and the "
-                         "roofline block never come from these contended launches: they are timed in extra single-stream "
-                         "passes after the timed region (see --single-stream)")
+                         "roofline block of --full never come from these contended launches: they are timed in extra "
+                         "single-stream passes after the timed region (see --single-stream)")
     ap.add_argument("--single-stream", action="store_true",
                     help="one stream, one chunk of all frames, in the timed region too: every kernel has the GPU to itself, so "
                          "rocprofv3 --kernel-trace of THIS command reports the durations of the kernel table "
@@ -378,18 +384,22 @@ def main():
                          "dfu3d_pseudo_boxes; same kernels, same results)")
     ap.add_argument("--graphs", action="store_true",
                     help="replay one captured hipGraph per chunk (measured slower than stream launches on ROCm 7.2)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="measure and check everything besides `value` as well: mask-packing cost, kernel table and roofline "
+                         "(--timing-steps), big-pool radius filter (--rf-big-frames), measured copy rate, CPU baselines "
+                         "(--cpu-procs) and the `parity` block against the oracle.  The timed steps are the same either way")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: no CPU baselines, no `parity` block")
     ap.add_argument("--cpu-procs", type=int, default=-1,
-                    help="host processes of the all-cores CPU figure (-1 = every core this job may use: affinity mask cut "
-                         "to the cgroup CPU quota; 0 = skip; forked before the GPU is initialised)")
+                    help="with --full: host processes of the all-cores CPU figure (-1 = every core this job may use: affinity "
+                         "mask cut to the cgroup CPU quota; 0 = skip; forked before the GPU is initialised)")
     ap.add_argument("--rf-big-frames", type=int, default=192,
-                    help="radius filter once more on the pool of this many frames in ONE launch (0 = skip): the default "
-                         "step's shadow (92 / 184 MB) fits the 256 MiB memory-side cache it has just been written "
+                    help="with --full: radius filter once more on the pool of this many frames in ONE launch (0 = skip): the "
+                         "default step's shadow (92 / 184 MB) fits the 256 MiB memory-side cache it has just been written "
                          "through, a 192-frame pool (550 MB) does not -- the HBM-resident figure next to the cache-resident one")
-    ap.add_argument("--no-kernel-timing", action="store_true")
+    ap.add_argument("--no-kernel-timing", action="store_true", help="with --full: no kernel table, roofline or big pool")
     ap.add_argument("--timing-steps", type=int, default=3,
-                    help="extra passes AFTER the timed region in which every stage is bracketed with HIP events on the "
-                         "launch stream (one stream, one chunk)")
+                    help="with --full: extra passes AFTER the timed region in which every stage is bracketed with HIP events "
+                         "on the launch stream (one stream, one chunk)")
     ap.add_argument("--dump", type=str, default="", help="write the JSON here as well")
     ap.add_argument("--dump-outputs", type=str, default="", metavar="DIR",
                     help="after the timed region, write the box rows of the last timed step (what the path returns to its "
@@ -410,7 +420,7 @@ def main():
                       or any(k.upper().startswith(("ROCPROF", "ROCP_", "ROCTRACER")) for k in os.environ))
     avail = usable_cores()
     n_cpu = avail if args.cpu_procs < 0 else min(args.cpu_procs, avail)
-    if (int(os.environ.get("WORLD_SIZE", "1")) == 1 and not args.no_cpu_baseline and n_cpu > 0
+    if (args.full and int(os.environ.get("WORLD_SIZE", "1")) == 1 and not args.no_cpu_baseline and n_cpu > 0
             and not torch.cuda.is_initialized() and not under_profiler):   # a profiler's preload already owns the GPU
         try:
             cpu_pool = cpu_all_cores_start(n_cpu)
@@ -453,7 +463,7 @@ def main():
         planes = batch.masks
         batch.pack_masks()
         mask_word = batch.mask_format
-        if rank == 0:
+        if rank == 0 and args.full:
             from dfu3d_amd import stages as _st
             V_, M_ = planes.shape[0], planes.shape[1]
             e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
@@ -465,7 +475,7 @@ def main():
             pack_ms = e0.elapsed_time(e1) / 3
         del planes
     cpu_scenes = None
-    if rank == 0 and not args.no_cpu_baseline:
+    if rank == 0 and args.full and not args.no_cpu_baseline:
         keep = scenes[:10]
         cpu_scenes = [synth.Scene(s.points.cpu(), s.calibs, s.depth.cpu(), s.masks.cpu(), s.n_inst,
                                   s.inst_class, s.inst_box, s.inst_score, s.boxes3d) for s in keep]
@@ -557,7 +567,7 @@ def main():
 
     # ---- kernel table: extra passes after the timed region, one stream, one chunk, every stage bracketed ----
     kern, counts, tsteps = {}, {}, 0
-    if rank == 0 and not args.no_kernel_timing and args.timing_steps > 0:
+    if rank == 0 and args.full and not args.no_kernel_timing and args.timing_steps > 0:
         if args.lanes != 1 or chunk_frames != frames:
             del eng
             torch.cuda.empty_cache()
@@ -574,7 +584,7 @@ def main():
         counts = eng.counters()
     # ---- radius filter on a pool larger than the memory-side cache (one launch over --rf-big-frames frames) ----
     rf_big = None
-    if (rank == 0 and world == 1 and not args.no_kernel_timing and args.timing_steps > 0 and args.rf_big_frames > frames
+    if (rank == 0 and world == 1 and args.full and not args.no_kernel_timing and args.timing_steps > 0 and args.rf_big_frames > frames
             and dense):
         try:
             del eng
@@ -606,7 +616,7 @@ def main():
             torch.cuda.empty_cache()
         except Exception as e:                                       # never lose the timing line
             rf_big = {"error": repr(e)}
-    copy_rate = measure_copy_rate(dev) if rank == 0 else None
+    copy_rate = measure_copy_rate(dev) if rank == 0 and args.full else None
 
     if rank == 0:
         total_frames = args.steps * frames * world
@@ -623,8 +633,9 @@ def main():
                                       args.boxes[0], args.boxes[1]),
                        "frames_per_gpu_per_step": frames, "views_per_launch_chunk": views, "streams": args.lanes,
                        "boxes_per_step_all_ranks": n_boxes, "parallelism": "frames sharded x%d" % world},
-            "hbm_copy_GBs_measured": round(copy_rate, 1),
         }
+        if copy_rate is not None:
+            out["hbm_copy_GBs_measured"] = round(copy_rate, 1)
         if dumped is not None:
             out["dumped_outputs"] = {"dir": os.path.abspath(args.dump_outputs), "files": dumped,
                                      "columns": list(D.GATHER_COLUMNS)}
@@ -723,6 +734,9 @@ def main():
             out["cpu_baseline"] = {"value": round(fps, 4), "unit": "frames/s", "cores": 1, "kind": "port",
                                    "sample": "%d of the same synthetic frames (6 cams each) through oracle/penet_oracle.py "
                                              "(NumPy + C, 1 thread) in %.1fs; host has %d cores" % (nf, secs, os.cpu_count())}
+        elif repeat.get("identical") is False:       # (compared inside the timed steps whatever the options)
+            log("[bench] PARITY FAILED: the rows of the last two timed steps differ")
+            out["parity_failed"] = True
         if cpu_pool is not None:
             cpu_all_cores_cancel(cpu_pool)
         if args.dump:

@@ -6,7 +6,7 @@ number in tracked prose is typed by hand.
 
 Inputs (profiles/):  <r>_kernel_stats_bench_single_stream.csv, <r>_kernel_stats_bench_default.csv (rocprofv3
 --kernel-trace --stats), <r>_pmc_traffic.json (FETCH_SIZE / WRITE_SIZE passes), <r>_pmc_sq.json (SQ counters),
-<r>_isa_mix.txt (tools/isa_mix.py over csrc/*.hip), <r>_bench_default.json (the line of `python bench.py`).
+<r>_isa_mix.txt (tools/isa_mix.py over csrc/*.hip), <r>_bench_default.json (the line of `python bench.py --full`).
 A generated block sits between `<!-- BEGIN GENERATED <name> (tools/render_numbers.py) -->` and `<!-- END GENERATED <name> -->`
 in profiles/README_<r>.md and DESIGN.md; everything outside the markers is prose and is left alone."""
 import csv
