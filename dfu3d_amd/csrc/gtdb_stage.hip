@@ -11,36 +11,9 @@
 // headers in scope; both are within one float32 ulp of this choice -- hazard noted
 // in DESIGN.md, row f-2).
 #include "common.hpp"
+#include "pt_in_box.hpp"
 
 namespace {
-
-struct BoxF {
-  float cx, cy, cz, cosa, sina;
-  double hz, hx, hy;          // dz/2, dx/2 + MARGIN, dy/2 + MARGIN (double, as the reference compares)
-  double c64x, c64y, c64z;    // float64 centre: gt_points[:, :3] -= gt_boxes[i, :3] (kitti_dataset.py:319)
-};
-
-__device__ __forceinline__ BoxF load_box(const double *b) {
-  BoxF q;
-  q.c64x = b[0]; q.c64y = b[1]; q.c64z = b[2];
-  q.cx = (float)b[0]; q.cy = (float)b[1]; q.cz = (float)b[2];          // boxes.float()
-  const float dx = (float)b[3], dy = (float)b[4], dz = (float)b[5], rz = (float)b[6];
-  const float MARGIN = 1e-2f;
-  q.cosa = (float)cos((double)(-rz));
-  q.sina = (float)sin((double)(-rz));
-  q.hz = (double)dz / 2.0;
-  q.hx = (double)dx / 2.0 + (double)MARGIN;
-  q.hy = (double)dy / 2.0 + (double)MARGIN;
-  return q;
-}
-
-__device__ __forceinline__ bool pt_in_box(const BoxF &q, float x, float y, float z) {
-  if ((double)fabsf(z - q.cz) > q.hz) return false;
-  const float sx = x - q.cx, sy = y - q.cy;
-  const float lx = sx * q.cosa + sy * (-q.sina);
-  const float ly = sx * q.sina + sy * q.cosa;
-  return ((double)fabsf(lx) < q.hx) && ((double)fabsf(ly) < q.hy);
-}
 
 // (B, n) int32 indicator, the return value of roiaware_pool3d_utils.points_in_boxes_cpu
 __global__ __launch_bounds__(256) void k_pib_mask(const float *__restrict__ pts, int n, int stride,

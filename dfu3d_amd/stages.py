@@ -605,3 +605,77 @@ def lshape_fit(px, py, pz, label, seg_base, seg_cnt, S, max_inst, calib, inst_cl
 
 def status_message(word):
     return "; ".join(t for b, t in STATUS_TEXT.items() if word & b) or "ok"
+
+
+ST_BOX_RANGE = 64                      # dfu3d_gt_sample_*: a scene beyond the box cap / max_scene_points
+GT_SAMPLE_MAX_BOXES = 512              # DFU3D_GT_SAMPLE_MAX_BOXES
+
+
+def gt_sample_collide(boxes, box_off, gt_cnt, grp, gt_mask, max_boxes, status):
+    """Ground-truth sampling, collision step (dfu3d_gt_sample_collide).  boxes float64 (Nt,7), box_off int32 (B+1),
+    gt_cnt int32 (B), grp / gt_mask int32 (Nt) -> accept int32 (Nt), out_boxes float64 (Nt,7), out_src int32 (Nt),
+    out_cnt int32 (B)."""
+    nt, B = int(boxes.shape[0]), int(gt_cnt.shape[0])
+    if max_boxes > GT_SAMPLE_MAX_BOXES:
+        raise Dfu3dError("gt_sample: a scene has %d boxes (ground truths + candidates), at most %d"
+                         % (max_boxes, GT_SAMPLE_MAX_BOXES))
+    dev = boxes.device
+    n1 = max(nt, 1)                    # never a null pointer for an empty batch of boxes
+    accept = torch.zeros(n1, dtype=torch.int32, device=dev)
+    out_boxes = torch.zeros((n1, 7), dtype=torch.float64, device=dev)
+    out_src = torch.zeros(n1, dtype=torch.int32, device=dev)
+    out_cnt = torch.zeros(max(B, 1), dtype=torch.int32, device=dev)
+    if nt == 0:
+        boxes = torch.zeros((1, 7), dtype=torch.float64, device=dev)
+        grp = torch.zeros(1, dtype=torch.int32, device=dev)
+        gt_mask = torch.zeros(1, dtype=torch.int32, device=dev)
+    rc = _lib.lib().dfu3d_gt_sample_collide(
+        _chk(boxes, "boxes", torch.float64, numel=n1 * 7), _chk(box_off, "box_off", torch.int32, numel=B + 1),
+        _chk(gt_cnt, "gt_cnt", torch.int32, numel=B), _chk(grp, "grp", torch.int32, numel=n1),
+        _chk(gt_mask, "gt_mask", torch.int32, numel=n1), B, int(max_boxes),
+        _chk(accept, "accept", torch.int32, numel=n1), _chk(out_boxes, "out_boxes", torch.float64, numel=n1 * 7),
+        _chk(out_src, "out_src", torch.int32, numel=n1), _chk(out_cnt, "out_cnt", torch.int32, min_numel=B),
+        _chk(status, "status", torch.int32, numel=1), _stream())
+    _lib.check(rc, "dfu3d_gt_sample_collide")
+    return accept[:nt], out_boxes[:nt], out_src[:nt], out_cnt[:B]
+
+
+def gt_sample_paste_scratch_bytes(B, max_scene_points):
+    n = int(_lib.lib().dfu3d_gt_sample_paste_scratch_bytes(int(B), int(max_scene_points)))
+    if n < 0:
+        raise Dfu3dError("gt_sample_paste_scratch_bytes: impossible sizes")
+    return n
+
+
+def gt_sample_paste(points, pt_off, max_scene_points, box_off, gt_cnt, boxes, large, accept, pool, obj_src, obj_cnt,
+                    cap_out, status):
+    """Ground-truth sampling, point step (dfu3d_gt_sample_paste).  points float32 (N,C) by scene (pt_off int64 (B+1)),
+    pool float32 (P,C); per box row: boxes / large float64 (Nt,7), accept / obj_cnt int32, obj_src int64 ->
+    out float32 (cap_out,C), out_off int64 (B+1) (dense CSR)."""
+    B = int(gt_cnt.shape[0])
+    C = int(points.shape[1])
+    dev = points.device
+    nt = int(boxes.shape[0])
+    if nt == 0:                        # every per-row operand non-null
+        boxes = large = torch.zeros((1, 7), dtype=torch.float64, device=dev)
+        accept = obj_cnt = torch.zeros(1, dtype=torch.int32, device=dev)
+        obj_src = torch.zeros(1, dtype=torch.int64, device=dev)
+    n1 = max(nt, 1)
+    if pool is not None and (pool.dim() != 2 or int(pool.shape[1]) != C):
+        raise Dfu3dError("gt_sample_paste: pool must be (P, %d)" % C)
+    out = torch.empty((max(int(cap_out), 1), C), dtype=torch.float32, device=dev)
+    out_off = torch.zeros(B + 1, dtype=torch.int64, device=dev)
+    scratch = torch.empty((gt_sample_paste_scratch_bytes(B, max_scene_points) + 7) // 8, dtype=torch.int64,
+                          device=dev)
+    pool_p = None if pool is None or pool.numel() == 0 else _chk(pool, "pool", torch.float32)
+    rc = _lib.lib().dfu3d_gt_sample_paste(
+        _chk(points, "points", torch.float32, numel=int(points.shape[0]) * C), C,
+        _chk(pt_off, "pt_off", torch.int64, numel=B + 1), B, int(max_scene_points),
+        _chk(box_off, "box_off", torch.int32, numel=B + 1), _chk(gt_cnt, "gt_cnt", torch.int32, numel=B),
+        _chk(boxes, "boxes", torch.float64, numel=n1 * 7), _chk(large, "large", torch.float64, numel=n1 * 7),
+        _chk(accept, "accept", torch.int32, numel=n1), pool_p, _chk(obj_src, "obj_src", torch.int64, numel=n1),
+        _chk(obj_cnt, "obj_cnt", torch.int32, numel=n1), _chk(out, "out", torch.float32, numel=out.shape[0] * C),
+        _chk(out_off, "out_off", torch.int64, numel=B + 1), int(cap_out), ctypes.c_void_p(scratch.data_ptr()),
+        _chk(status, "status", torch.int32, numel=1), _stream())
+    _lib.check(rc, "dfu3d_gt_sample_paste")
+    return out, out_off

@@ -55,6 +55,7 @@ extern "C" {
 #define DFU3D_ST_BIN_RANGE 8u       /* a spherical bin fell outside the table   */
 #define DFU3D_ST_VOX_PTS_OVERFLOW 16u /* overflow-bin list too small            */
 #define DFU3D_ST_VOXEL_RANGE 32u    /* dfu3d_voxel_down_sample: a segment wider than 2^21 voxels along an axis */
+#define DFU3D_ST_BOX_RANGE 64u      /* dfu3d_gt_sample_*: a scene beyond DFU3D_GT_SAMPLE_MAX_BOXES / max_scene_points */
 
 int dfu3d_version(void);
 const char *dfu3d_strerror(int code);
@@ -425,6 +426,39 @@ int dfu3d_eval_match_stats(int32_t metric, int32_t F, int32_t max_dt, const int6
 int dfu3d_la_sampling(const float *points, int32_t n_cols, const int64_t *obj_off, int32_t B,
                       float vert_res, float hor_res, float *out, int32_t *out_cnt, void *scratch,
                       int64_t n_points, void *stream);
+
+/* ---- f-5: ground-truth sampling (copy-paste augmentation) over the GT database -------------------------------------
+ * (pcdet/datasets/augmentor/database_sampler.py:364-501, DataBaseSampler.add_sampled_boxes_to_scene / __call__)
+ * A batch of B scenes.  The host draws every scene's candidates (the RNG part); these two calls do the rest.
+ * Box rows: float64 (Nt,7) [x y z dx dy dz heading]; scene b owns rows [box_off[b], box_off[b+1]), its gt_cnt[b] ground
+ * truths first, then its candidates ordered by class group, grp[row] = the group's rank (non-decreasing; ground-truth
+ * rows: -1), gt_mask[row] = the scene's gt_boxes_mask for ground-truth rows.  At most DFU3D_GT_SAMPLE_MAX_BOXES rows per
+ * scene (max_boxes: the largest count of the batch; DFU3D_ERANGE beyond, DFU3D_ST_BOX_RANGE if a scene exceeds it).
+ * dfu3d_gt_sample_collide: one workgroup per scene.  Group by group a candidate is accepted iff its BEV overlap (the
+ *   exact float32 area of dfu3d_boxes_bev, boxes rounded to float32) is 0 with every ground truth, with every candidate
+ *   accepted in an earlier group and with every other candidate of its group.  accept[row] = 1 / 0 (0 for ground-truth
+ *   rows); the scene's output boxes at [box_off[b], box_off[b] + out_cnt[b]): all ground truths if nothing was accepted,
+ *   else those with gt_mask != 0, then the accepted candidates; out_src = their row index within the scene.
+ * dfu3d_gt_sample_paste: points float32 (N, C), scene b owns rows [pt_off[b], pt_off[b+1]), at most max_scene_points
+ *   of them.  large (Nt,7): the candidates' boxes enlarged by REMOVE_EXTRA_WIDTH, float32 values; a scene point is kept
+ *   iff it lies in none of the scene's accepted large boxes (points_in_boxes_cpu, as dfu3d_points_in_boxes_mask).
+ *   pool float32 (P, C): the database's object points, candidate row r owns pool rows [obj_src[r], obj_src[r]+obj_cnt[r]).
+ *   out float32 (cap_out, C), dense CSR out_off (B+1): scene b = the accepted candidates' pool rows in acceptance order
+ *   with xyz + float32(boxes[r][0:3]), then its kept points in order.  cap_out >= N + sum of all candidates' obj_cnt
+ *   can never overflow (beyond cap_out: DFU3D_ST_POOL_OVERFLOW, rows cut).  pool may be NULL when no candidate has rows.
+ *   scratch: dfu3d_gt_sample_paste_scratch_bytes(B, max_scene_points) bytes, 8-byte aligned. */
+#define DFU3D_GT_SAMPLE_MAX_BOXES 512
+int dfu3d_gt_sample_collide(const double *boxes, const int32_t *box_off, const int32_t *gt_cnt,
+                            const int32_t *grp, const int32_t *gt_mask, int32_t B, int32_t max_boxes,
+                            int32_t *accept, double *out_boxes, int32_t *out_src, int32_t *out_cnt,
+                            uint32_t *status, void *stream);
+int64_t dfu3d_gt_sample_paste_scratch_bytes(int32_t B, int32_t max_scene_points);
+int dfu3d_gt_sample_paste(const float *points, int32_t C, const int64_t *pt_off, int32_t B,
+                          int32_t max_scene_points, const int32_t *box_off, const int32_t *gt_cnt,
+                          const double *boxes, const double *large, const int32_t *accept,
+                          const float *pool, const int64_t *obj_src, const int32_t *obj_cnt,
+                          float *out, int64_t *out_off, int64_t cap_out, void *scratch, uint32_t *status,
+                          void *stream);
 
 /* ---- self test of the two-tier bin classification ---------------------------
  * dfu3d_backproject_bin decides a pixel's spherical bin in float32 when every float32 estimate is farther from
