@@ -122,6 +122,10 @@ SIGNATURES = {
     "dfu3d_gt_sample_paste_scratch_bytes": (c_i64, [c_i32, c_i32]),
     "dfu3d_gt_sample_paste": (c_i32, [_P, c_i32, _P, c_i32, c_i32, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, c_i64,
                                       _P, _P, _P]),
+    "dfu3d_center_assign": (c_i32, [_P, c_i32, c_i32, c_i32, _P, c_i32, _P, c_i32, c_i32, c_i32] + [ctypes.c_float] * 4
+                            + [c_i32, c_i32, c_f64, c_i32] + [_P] * 7),
+    "dfu3d_center_decode": (c_i32, [_P] * 8 + [c_i32] * 5 + [ctypes.c_float] * 4 + [c_i32, _P, c_i32, ctypes.c_float]
+                            + [_P] * 6),
     "dfu3d_selftest_classify": (c_i32, [_P, c_i32, c_i32, _P, c_i32, c_i64, ctypes.c_uint64, c_f64, c_f64, _P, _P, _P]),
     "dfu3d_selftest_backproject": (c_i32, [_P, c_i32, c_i32, c_i64, ctypes.c_uint64, c_f64, c_f64, _P, _P, _P]),
     "dfu3d_lshape_fit_ws_doubles": (c_i64, [c_i64, c_i32]),

@@ -1,0 +1,139 @@
+"""The box geometry of pcdet/models/dense_heads/center_head.py as a plain object (the network stays the reference's):
+`assign_targets` and `generate_predicted_boxes` with the reference's arguments and returns, on
+csrc/centerhead_stage.hip (dfu3d_center_assign / dfu3d_center_decode).
+
+`assign_targets` launches one chain for all heads and samples and neither synchronises nor copies to the host.  More
+than NUM_MAX_OBJS boxes of one head in one sample (where the reference raises) set a bit in `self.status`, a device
+int32 the call resets: `assign_targets(..., check=True)` reads it and raises, otherwise `check_status()` does at the
+caller's next natural synchronisation.
+
+Divergence from the reference: `gt_boxes` is not written (the reference leaves head-local class ids in its last column) and
+boxes are assigned by the caller's original class ids."""
+import numpy as np
+import torch
+
+from . import centernet_utils, model_nms_utils
+from .. import stages
+from .._lib import Dfu3dError
+
+
+def _get(cfg, key, *default):
+    if isinstance(cfg, dict):
+        return cfg[key] if not default else cfg.get(key, default[0])
+    return getattr(cfg, key) if not default else getattr(cfg, key, default[0])
+
+
+class CenterHead:
+    def __init__(self, model_cfg, class_names, point_cloud_range, voxel_size, device='cuda'):
+        self.model_cfg = model_cfg
+        self.class_names = list(class_names)
+        self.point_cloud_range = point_cloud_range
+        self.voxel_size = voxel_size
+        self.device = torch.device(device)
+        self.feature_map_stride = _get(_get(model_cfg, 'TARGET_ASSIGNER_CONFIG'), 'FEATURE_MAP_STRIDE', None)
+        self.class_names_each_head = []
+        self.class_id_mapping_each_head = []
+        for cur_class_names in _get(model_cfg, 'CLASS_NAMES_EACH_HEAD'):
+            names = [x for x in cur_class_names if x in self.class_names]
+            self.class_names_each_head.append(names)
+            self.class_id_mapping_each_head.append(
+                torch.tensor([self.class_names.index(x) for x in names], dtype=torch.int64, device=self.device))
+        total = sum(len(x) for x in self.class_names_each_head)
+        assert total == len(self.class_names), 'class_names_each_head=%s' % (self.class_names_each_head,)
+        tab = -np.ones((len(self.class_names) + 1, 2), np.int32)
+        plane = [0]
+        for h, names in enumerate(self.class_names_each_head):
+            for j, n in enumerate(names):
+                tab[self.class_names.index(n) + 1] = (h, j)
+            plane.append(plane[-1] + len(names))
+        self.head_plane = plane
+        self._cls_tab = torch.from_numpy(tab).to(self.device)
+        self._head_plane = torch.tensor(plane, dtype=torch.int32, device=self.device)
+        self.status = torch.zeros(1, dtype=torch.int32, device=self.device)
+        head_cfg = _get(model_cfg, 'SEPARATE_HEAD_CFG', None)
+        self.head_order = list(_get(head_cfg, 'HEAD_ORDER')) if head_cfg is not None else ['center', 'center_z', 'dim', 'rot']
+
+    def check_status(self):
+        """Raise if the last assign_targets met more than NUM_MAX_OBJS boxes of one head in one sample (one host read)."""
+        s = int(self.status.item())
+        if s & stages.ST_CENTER_OVERFLOW:
+            raise Dfu3dError("assign_targets: more than NUM_MAX_OBJS = %d boxes of one head in one sample"
+                             % _get(_get(self.model_cfg, 'TARGET_ASSIGNER_CONFIG'), 'NUM_MAX_OBJS'))
+        if s:
+            raise Dfu3dError("assign_targets: status %d (%s)" % (s, stages.status_message(s)))
+
+    def assign_targets(self, gt_boxes, feature_map_size=None, check=False, **kwargs):
+        """gt_boxes (B, M, C) float32 on the device, feature_map_size [H, W] -> the reference's ret_dict: per head
+        'heatmaps' (B, n_cls_head, H, W), 'target_boxes' (B, NUM_MAX_OBJS, C), 'inds', 'masks' (int64),
+        'target_boxes_src'; 'heatmap_masks' stays an empty list."""
+        cfg = _get(self.model_cfg, 'TARGET_ASSIGNER_CONFIG')
+        H, W = int(feature_map_size[0]), int(feature_map_size[1])
+        if gt_boxes.dtype != torch.float32:
+            raise Dfu3dError("assign_targets: gt_boxes must be float32, got %s" % gt_boxes.dtype)
+        gt_boxes = gt_boxes.contiguous()
+        B = gt_boxes.shape[0]
+        n_cls, n_heads = len(self.class_names), len(self.class_names_each_head)
+        self.status.zero_()
+        f = centernet_utils._f32
+        heat, tgt, inds, masks, src = stages.center_assign(
+            gt_boxes, self._cls_tab, self._head_plane, n_cls, n_heads, W, H,
+            (f(self.point_cloud_range[0]), f(self.point_cloud_range[1])), (f(self.voxel_size[0]), f(self.voxel_size[1])),
+            _get(cfg, 'FEATURE_MAP_STRIDE'), _get(cfg, 'NUM_MAX_OBJS'), _get(cfg, 'GAUSSIAN_OVERLAP'),
+            _get(cfg, 'MIN_RADIUS'), self.status)
+        ret_dict = {'heatmaps': [], 'target_boxes': [], 'inds': [], 'masks': [], 'heatmap_masks': [],
+                    'target_boxes_src': []}
+        hw = H * W
+        for h in range(n_heads):
+            p0, p1 = self.head_plane[h], self.head_plane[h + 1]
+            ret_dict['heatmaps'].append(heat[B * p0 * hw:B * p1 * hw].view(B, p1 - p0, H, W))
+            ret_dict['target_boxes'].append(tgt[h])
+            ret_dict['inds'].append(inds[h])
+            ret_dict['masks'].append(masks[h])
+            ret_dict['target_boxes_src'].append(src[h])
+        if check:
+            self.check_status()
+        return ret_dict
+
+    def generate_predicted_boxes(self, batch_size, pred_dicts):
+        """center_head.py:297-364: per head sigmoid / exp, the decode kernel, class mapping, optional IoU rectification,
+        NMS; heads concatenated per sample, labels + 1."""
+        post_process_cfg = _get(self.model_cfg, 'POST_PROCESSING')
+        nms_cfg = _get(post_process_cfg, 'NMS_CONFIG')
+        nms_type = _get(nms_cfg, 'NMS_TYPE')
+        limit = torch.tensor(_get(post_process_cfg, 'POST_CENTER_LIMIT_RANGE'), dtype=torch.float32, device=self.device)
+        ret_dict = [{'pred_boxes': [], 'pred_scores': [], 'pred_labels': []} for _ in range(batch_size)]
+        for idx, pred_dict in enumerate(pred_dicts):
+            final_pred_dicts = centernet_utils.decode_bbox_from_heatmap(
+                heatmap=pred_dict['hm'].sigmoid(), rot_cos=pred_dict['rot'][:, 0].unsqueeze(dim=1),
+                rot_sin=pred_dict['rot'][:, 1].unsqueeze(dim=1), center=pred_dict['center'],
+                center_z=pred_dict['center_z'], dim=pred_dict['dim'].exp(),
+                vel=pred_dict['vel'] if 'vel' in self.head_order else None,
+                iou=(pred_dict['iou'] + 1) * 0.5 if 'iou' in pred_dict else None,
+                point_cloud_range=self.point_cloud_range, voxel_size=self.voxel_size,
+                feature_map_stride=self.feature_map_stride, K=_get(post_process_cfg, 'MAX_OBJ_PER_SAMPLE'),
+                circle_nms=(nms_type == 'circle_nms'), score_thresh=_get(post_process_cfg, 'SCORE_THRESH'),
+                post_center_limit_range=limit)
+            for k, final_dict in enumerate(final_pred_dicts):
+                final_dict['pred_labels'] = self.class_id_mapping_each_head[idx][final_dict['pred_labels'].long()]
+                if _get(post_process_cfg, 'USE_IOU_TO_RECTIFY_SCORE', False) and 'pred_iou' in final_dict:
+                    pred_iou = torch.clamp(final_dict['pred_iou'], min=0, max=1.0)
+                    rect = final_dict['pred_scores'].new_tensor(_get(post_process_cfg, 'IOU_RECTIFIER'))
+                    final_dict['pred_scores'] = torch.pow(final_dict['pred_scores'], 1 - rect[final_dict['pred_labels']]) \
+                        * torch.pow(pred_iou, rect[final_dict['pred_labels']])
+                if nms_type == 'class_specific_nms':
+                    selected, selected_scores = model_nms_utils.class_specific_nms(
+                        box_scores=final_dict['pred_scores'], box_preds=final_dict['pred_boxes'],
+                        box_labels=final_dict['pred_labels'], nms_config=nms_cfg,
+                        score_thresh=_get(nms_cfg, 'SCORE_THRESH', None))
+                else:
+                    selected, selected_scores = model_nms_utils.class_agnostic_nms(
+                        box_scores=final_dict['pred_scores'], box_preds=final_dict['pred_boxes'], nms_config=nms_cfg,
+                        score_thresh=None)
+                ret_dict[k]['pred_boxes'].append(final_dict['pred_boxes'][selected])
+                ret_dict[k]['pred_scores'].append(selected_scores)
+                ret_dict[k]['pred_labels'].append(final_dict['pred_labels'][selected])
+        for k in range(batch_size):
+            ret_dict[k]['pred_boxes'] = torch.cat(ret_dict[k]['pred_boxes'], dim=0)
+            ret_dict[k]['pred_scores'] = torch.cat(ret_dict[k]['pred_scores'], dim=0)
+            ret_dict[k]['pred_labels'] = torch.cat(ret_dict[k]['pred_labels'], dim=0) + 1
+        return ret_dict

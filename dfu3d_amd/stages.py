@@ -679,3 +679,71 @@ def gt_sample_paste(points, pt_off, max_scene_points, box_off, gt_cnt, boxes, la
         _chk(status, "status", torch.int32, numel=1), _stream())
     _lib.check(rc, "dfu3d_gt_sample_paste")
     return out, out_off
+
+
+ST_CENTER_OVERFLOW = 128               # dfu3d_center_assign: more than num_max_objs boxes of one head in one sample
+CENTER_MAX_K = 1024                    # DFU3D_CENTER_MAX_K
+STATUS_TEXT[ST_CENTER_OVERFLOW] = "center_assign: more than num_max_objs boxes of one head in one sample"
+
+
+def center_assign(gt_boxes, cls_tab, head_plane, n_cls, n_heads, W, H, range_xy, voxel_xy, stride, num_max_objs,
+                  gaussian_overlap, min_radius, status):
+    """CenterHead target assignment for all heads and samples (dfu3d_center_assign).  gt_boxes float32 (B,M,C) ->
+    heat float32 (B * n_cls * H * W, head-major), target_boxes / target_boxes_src float32 (n_heads,B,num_max_objs,C),
+    inds / masks int64 (n_heads,B,num_max_objs).  Nothing here synchronises or copies to the host."""
+    if gt_boxes.dim() != 3 or gt_boxes.shape[2] < 8:
+        raise Dfu3dError("center_assign: gt_boxes must be (B, M, C >= 8), got %s" % (tuple(gt_boxes.shape),))
+    B, M, C = (int(v) for v in gt_boxes.shape)
+    dev = gt_boxes.device
+    heat = torch.empty(max(B * n_cls * H * W, 1), dtype=torch.float32, device=dev)
+    tgt = torch.empty((n_heads, B, num_max_objs, C), dtype=torch.float32, device=dev)
+    src = torch.empty((n_heads, B, num_max_objs, C), dtype=torch.float32, device=dev)
+    inds = torch.empty((n_heads, B, num_max_objs), dtype=torch.int64, device=dev)
+    masks = torch.empty((n_heads, B, num_max_objs), dtype=torch.int64, device=dev)
+    if B == 0:
+        return heat[:0], tgt, inds, masks, src
+    gt_p = _chk(gt_boxes, "gt_boxes", torch.float32) if B * M else None
+    rc = _lib.lib().dfu3d_center_assign(
+        gt_p, B, M, C, _chk(cls_tab, "cls_tab", torch.int32, numel=2 * (n_cls + 1)), int(n_cls),
+        _chk(head_plane, "head_plane", torch.int32, numel=n_heads + 1), int(n_heads), int(W), int(H),
+        float(range_xy[0]), float(range_xy[1]), float(voxel_xy[0]), float(voxel_xy[1]), int(stride), int(num_max_objs),
+        float(gaussian_overlap), int(min_radius), _chk(heat, "heat", torch.float32),
+        _chk(tgt, "target_boxes", torch.float32), _chk(inds, "inds", torch.int64), _chk(masks, "masks", torch.int64),
+        _chk(src, "target_boxes_src", torch.float32), _chk(status, "status", torch.int32, numel=1), _stream())
+    _lib.check(rc, "dfu3d_center_assign")
+    return heat, tgt, inds, masks, src
+
+
+def center_decode(heat, rot_cos, rot_sin, center, center_z, dim, vel, iou, K, range_xy, voxel_xy, stride, limit,
+                  score_thresh):
+    """Top-K decode of a batch of head outputs (dfu3d_center_decode).  heat float32 (B,n_cls,H,W) and the regression
+    maps -> boxes float32 (B,K,7|9), scores (B,K), labels int32 (B,K), iou (B,K) or None, count int32 (B); the first
+    count[b] rows of sample b are valid."""
+    if heat.dim() != 4:
+        raise Dfu3dError("center_decode: heatmap must be (B, n_cls, H, W)")
+    B, n_cls, H, W = (int(v) for v in heat.shape)
+    if K > CENTER_MAX_K:
+        raise Dfu3dError("center_decode: K = %d, at most %d" % (K, CENTER_MAX_K))
+    dev = heat.device
+    nb = 9 if vel is not None else 7
+    boxes = torch.empty((B, K, nb), dtype=torch.float32, device=dev)
+    scores = torch.empty((B, K), dtype=torch.float32, device=dev)
+    labels = torch.empty((B, K), dtype=torch.int32, device=dev)
+    iou_out = torch.empty((B, K), dtype=torch.float32, device=dev) if iou is not None else None
+    count = torch.zeros(max(B, 1), dtype=torch.int32, device=dev)
+    if B == 0:
+        return boxes, scores, labels, iou_out, count[:0]
+    hw = B * H * W
+    rc = _lib.lib().dfu3d_center_decode(
+        _chk(heat, "heatmap", torch.float32), _chk(rot_cos, "rot_cos", torch.float32, numel=hw),
+        _chk(rot_sin, "rot_sin", torch.float32, numel=hw), _chk(center, "center", torch.float32, numel=2 * hw),
+        _chk(center_z, "center_z", torch.float32, numel=hw), _chk(dim, "dim", torch.float32, numel=3 * hw),
+        None if vel is None else _chk(vel, "vel", torch.float32, numel=2 * hw),
+        None if iou is None else _chk(iou, "iou", torch.float32, numel=hw), B, n_cls, H, W, int(K),
+        float(range_xy[0]), float(range_xy[1]), float(voxel_xy[0]), float(voxel_xy[1]), int(stride),
+        _chk(limit, "post_center_limit_range", torch.float32, numel=6), 0 if score_thresh is None else 1,
+        0.0 if score_thresh is None else float(score_thresh), _chk(boxes, "boxes", torch.float32),
+        _chk(scores, "scores", torch.float32), _chk(labels, "labels", torch.int32),
+        None if iou_out is None else _chk(iou_out, "iou_out", torch.float32), _chk(count, "count", torch.int32), _stream())
+    _lib.check(rc, "dfu3d_center_decode")
+    return boxes, scores, labels, iou_out, count

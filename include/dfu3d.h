@@ -56,6 +56,7 @@ extern "C" {
 #define DFU3D_ST_VOX_PTS_OVERFLOW 16u /* overflow-bin list too small            */
 #define DFU3D_ST_VOXEL_RANGE 32u    /* dfu3d_voxel_down_sample: a segment wider than 2^21 voxels along an axis */
 #define DFU3D_ST_BOX_RANGE 64u      /* dfu3d_gt_sample_*: a scene beyond DFU3D_GT_SAMPLE_MAX_BOXES / max_scene_points */
+#define DFU3D_ST_CENTER_OVERFLOW 128u /* dfu3d_center_assign: more than num_max_objs boxes of one head in one sample */
 
 int dfu3d_version(void);
 const char *dfu3d_strerror(int code);
@@ -459,6 +460,43 @@ int dfu3d_gt_sample_paste(const float *points, int32_t C, const int64_t *pt_off,
                           const float *pool, const int64_t *obj_src, const int32_t *obj_cnt,
                           float *out, int64_t *out_off, int64_t cap_out, void *scratch, uint32_t *status,
                           void *stream);
+
+/* ---- f-6: CenterHead target assignment and box decoding ---------------------------------------------------------------
+ * (pcdet/models/dense_heads/center_head.py:106-227 assign_targets; pcdet/models/model_utils/centernet_utils.py:9-69 and
+ * :155-241 decode_bbox_from_heatmap)
+ * dfu3d_center_assign: all heads and all samples of a batch.  gt_boxes float32 (B, M, C), C >= 8: x y z dx dy dz yaw
+ *   [C - 8 more columns] class, class = 1-based id over the detector's n_cls classes, 0 (or anything outside 1..n_cls) =
+ *   no box.  cls_tab int32 (n_cls + 1, 2): row c = (head, 0-based id within the head) of class c, row 0 = (-1, -1).
+ *   head_plane int32 (n_heads + 1): head_plane[h] = number of classes of the heads before h.  Map of W x H cells (x, y);
+ *   range / voxel: the float32 values of point_cloud_range[0:2] and voxel_size[0:2].  Outputs, head-major:
+ *   heat float32, head h at float offset B * head_plane[h] * H * W as (B, classes of h, H, W), zeroed by the call;
+ *   target_boxes / target_boxes_src float32 (n_heads, B, num_max_objs, C), inds / masks int64 (n_heads, B, num_max_objs),
+ *   every slot written.  Slot k of (head, sample) = the k-th box of the sample, in input order, whose class belongs to the
+ *   head: src = the row with its class replaced by the 1-based id within the head; if dx > 0 and dy > 0 (in cells) also
+ *   mask = 1, inds = cy * W + cx, target = [cx - int(cx), cy - int(cy), z, log(dx dy dz), cos(yaw), sin(yaw), extra
+ *   columns] and a Gaussian of the reference's radius (gaussian_radius, float32) combined into the class plane with
+ *   max; the Gaussian is evaluated in fp64 and rounded to float32.  Boxes beyond num_max_objs of a (head, sample) are
+ *   dropped and DFU3D_ST_CENTER_OVERFLOW is set (the reference raises there).  gt_boxes is only read.
+ * dfu3d_center_decode: heat float32 (B, n_cls, H, W) (activated scores), rot_cos / rot_sin / center_z / iou (B, 1, H, W),
+ *   center / vel (B, 2, H, W), dim (B, 3, H, W); vel and iou may be NULL.  Per sample: the K largest scores, descending,
+ *   ties by ascending flat index class * H * W + cell, NaN above every number; rows [x y z dx dy dz angle (vx vy)] with
+ *   x = (col + center_x) * stride * voxel_x + range_x in float32, angle = atan2(sin, cos) evaluated in fp64; rows whose
+ *   x y z lie in [limit[0:3], limit[3:6]] and (use_thresh) whose score > score_thresh are kept, compacted in order:
+ *   boxes float32 (B, K, 7 | 9), scores float32 (B, K), labels int32 (B, K) (class plane), iou_out float32 (B, K) when iou
+ *   is given, count int32 (B); rows beyond count[b] are not written.  K <= DFU3D_CENTER_MAX_K (DFU3D_ERANGE beyond),
+ *   K <= n_cls * H * W. */
+#define DFU3D_CENTER_MAX_K 1024
+int dfu3d_center_assign(const float *gt_boxes, int32_t B, int32_t M, int32_t C, const int32_t *cls_tab, int32_t n_cls,
+                        const int32_t *head_plane, int32_t n_heads, int32_t W, int32_t H, float range_x, float range_y,
+                        float voxel_x, float voxel_y, int32_t stride, int32_t num_max_objs, double gaussian_overlap,
+                        int32_t min_radius, float *heat, float *target_boxes, int64_t *inds, int64_t *masks,
+                        float *target_boxes_src, uint32_t *status, void *stream);
+int dfu3d_center_decode(const float *heat, const float *rot_cos, const float *rot_sin, const float *center,
+                        const float *center_z, const float *dim, const float *vel, const float *iou, int32_t B,
+                        int32_t n_cls, int32_t H, int32_t W, int32_t K, float range_x, float range_y, float voxel_x,
+                        float voxel_y, int32_t stride, const float *limit, int32_t use_thresh, float score_thresh,
+                        float *boxes, float *scores, int32_t *labels, float *iou_out, int32_t *count, void *stream);
+
 
 /* ---- self test of the two-tier bin classification ---------------------------
  * dfu3d_backproject_bin decides a pixel's spherical bin in float32 when every float32 estimate is farther from
