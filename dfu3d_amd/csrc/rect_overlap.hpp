@@ -64,12 +64,19 @@ __device__ inline float overlap_area(const Rect &A, const Rect &B, float *pu, fl
       const int kn = (k + 1 == n) ? 0 : k + 1;
       const float u1 = iu[kn * IB], v1 = iv[kn * IB];
       const float g1 = lim + sg * ic[kn * IB];
-      if (g0 >= 0.0f) { ou[m * IB] = u0; ov[m * IB] = v0; m++; }
+      // the slot saturates at MAXV - 1 (a select, not a branch): eight is the bound in exact arithmetic, and inexact
+      // signs of g must not carry a ninth vertex into the next thread's column
+      if (g0 >= 0.0f) {
+        const int slot = min(m, MAXV - 1);
+        ou[slot * IB] = u0; ov[slot * IB] = v0;
+        m = min(m + 1, MAXV);
+      }
       if ((g0 >= 0.0f) != (g1 >= 0.0f)) {                             // the edge crosses the side
         const float t = g0 / (g0 - g1);
-        ou[m * IB] = u0 + t * (u1 - u0);
-        ov[m * IB] = v0 + t * (v1 - v0);
-        m++;
+        const int slot = min(m, MAXV - 1);
+        ou[slot * IB] = u0 + t * (u1 - u0);
+        ov[slot * IB] = v0 + t * (v1 - v0);
+        m = min(m + 1, MAXV);
       }
       u0 = u1; v0 = v1; g0 = g1;
     }

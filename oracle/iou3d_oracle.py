@@ -69,7 +69,11 @@ def _clip_pairs(PA, PB):
     xn, yn = np.take_along_axis(x, nxt, 1), np.take_along_axis(y, nxt, 1)
     live = idx[None, :] < n[:, None]
     area = 0.5 * np.abs(np.where(live, x * yn - xn * y, 0.0).sum(1))
-    return np.where(n >= 3, area, 0.0)
+    # a clip polygon without area (a segment or a point: some or all of its edges have no direction, so their half-plane
+    # test holds everywhere) encloses nothing
+    bx, by = PB[:, :, 0], PB[:, :, 1]
+    area_b = 0.5 * np.abs((bx * np.roll(by, -1, 1) - np.roll(bx, -1, 1) * by).sum(1))
+    return np.where((n >= 3) & (area_b > 0), area, 0.0)
 
 
 def _overlap_matrix(CA, CB):
@@ -151,6 +155,84 @@ def nms(boxes, scores, thresh, pre_maxsize=None, iou=None, normal=False):
         keep.append(i)
         dead[i + 1:] |= iou[i, i + 1:] > thresh
     return order[np.array(keep, np.int64)], iou
+
+
+# ---- sparse path: the same numbers without the n x n matrix (n = 32768 would need 8.6 GB) ------------------------------
+def pair_ious(boxes, normal=False, chunk=256):
+    """Boxes (n,7) in walk order -> (i, j, iou) float64 for every pair j > i whose circumscribed circles meet (the test
+    _overlap_matrix applies; every other pair has IoU exactly 0), sorted by (i, j).  The IoU of a pair is computed by the
+    same code on the same numbers as in the dense `nms`, so the values are identical to iou[i, j] there."""
+    b = np.asarray(boxes, np.float64).reshape(-1, 7)
+    n = b.shape[0]
+    C = _corners7(b)
+    ctr = C.mean(1) if n else np.zeros((0, 2))
+    rad = np.linalg.norm(C[:, 0] - ctr, axis=1) if n else np.zeros(0)
+    # row chunks in x order, so that a chunk only has to look at the columns of its own x range
+    by_x = np.argsort(ctr[:, 0], kind="stable")
+    xs = ctr[by_x, 0]
+    reach = 2 * rad.max() * (1 + 1e-9) + 1e-9 if n else 0.0
+    I_, J_ = [np.zeros(0, np.int64)], [np.zeros(0, np.int64)]
+    for r0 in range(0, n, chunk):
+        rows = by_x[r0:r0 + chunk]
+        c0, c1 = np.searchsorted(xs, [xs[r0] - reach, xs[min(r0 + chunk, n) - 1] + reach], side="left")
+        cols = by_x[c0:max(c1, min(r0 + chunk, n))]
+        d = np.linalg.norm(ctr[rows, None, :] - ctr[None, cols, :], axis=2)
+        ii, jj = np.nonzero(d <= (rad[rows, None] + rad[None, cols]) * (1 + 1e-9) + 1e-12)
+        ii, jj = rows[ii], cols[jj]
+        later = jj > ii
+        I_.append(ii[later]); J_.append(jj[later])
+    i, j = np.concatenate(I_), np.concatenate(J_)
+    by_ij = np.lexsort((j, i))
+    i, j = i[by_ij], j[by_ij]
+    s = b[:, 3] * b[:, 4]
+    if normal:
+        x0, x1 = b[:, 0] - b[:, 3] / 2, b[:, 0] + b[:, 3] / 2
+        y0, y1 = b[:, 1] - b[:, 4] / 2, b[:, 1] + b[:, 4] / 2
+        w = np.maximum(np.minimum(x1[i], x1[j]) - np.maximum(x0[i], x0[j]), 0)
+        h = np.maximum(np.minimum(y1[i], y1[j]) - np.maximum(y0[i], y0[j]), 0)
+        ov = w * h
+    else:
+        ov = np.zeros(i.size)
+        for p0 in range(0, i.size, 1 << 16):                          # bounded memory
+            ov[p0:p0 + (1 << 16)] = _clip_pairs(C[i[p0:p0 + (1 << 16)]], C[j[p0:p0 + (1 << 16)]])
+    return i, j, ov / np.maximum(s[i] + s[j] - ov, 1e-8)
+
+
+def nms_sparse(boxes, scores, thresh, pre_maxsize=None, normal=False, pairs=None):
+    """`nms` without the dense matrix -> (indices into the input of the kept boxes, best first; (i, j, iou) of
+    `pair_ious` on the score-sorted boxes).  `np.abs(iou - thresh) < d` on the third array answers which pairs lie
+    within d of the threshold.  pairs: a `pair_ious` result for the same boxes, order and mode, to walk several
+    thresholds over one list."""
+    order = np.argsort(-np.asarray(scores, np.float64), kind="stable")
+    if pre_maxsize is not None:
+        order = order[:pre_maxsize]
+    n = order.size
+    if pairs is None:
+        pairs = pair_ious(np.asarray(boxes, np.float64)[order], normal=normal)
+    i, j, iou = pairs
+    hit = iou > thresh
+    hi, hj = i[hit], j[hit]                                           # still sorted by i
+    start = np.searchsorted(hi, np.arange(n + 1))
+    dead = np.zeros(n, bool)
+    keep = []
+    for k in range(n):
+        if dead[k]:
+            continue
+        keep.append(k)
+        dead[hj[start[k]:start[k + 1]]] = True
+    return order[np.array(keep, np.int64)], pairs
+
+
+def widest_gap_threshold(values, nominal, window=0.01):
+    """A threshold near `nominal` that no value is close to: the midpoint of the widest gap between consecutive values
+    (the window's two ends count as values) inside [nominal - window, nominal + window] -> (threshold, half-width of
+    that gap).  Deterministic; the first of several equally wide gaps wins."""
+    v = np.asarray(values, np.float64)
+    v = np.unique(v[(v > nominal - window) & (v < nominal + window)])
+    v = np.concatenate([[nominal - window], v, [nominal + window]])
+    g = np.diff(v)
+    k = int(np.argmax(g))
+    return float(0.5 * (v[k] + v[k + 1])), float(0.5 * g[k])
 
 
 # ---- the reference's OWN overlap construction, for measuring how far it is from the exact area -------------------------

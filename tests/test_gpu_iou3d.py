@@ -1,23 +1,19 @@
 """f-3 on the GPU against the independent float64 checker (oracle/iou3d_oracle.py: world-frame polygon
 clipping, no code or formulation shared with the kernels): overlap / IoU within 1e-5 absolute, NMS keep lists identical
-unless a pair sits within float32 noise of the threshold."""
+at thresholds that no pair of the scene is near (tests/iou3d_cases.py).  Clipper edge cases: tests/test_gpu_iou3d_edges.py;
+NMS patterns with answers known in closed form: tests/test_gpu_nms_patterns.py."""
 import numpy as np
 import pytest
 import torch
 
 from oracle import iou3d_oracle as I
+from tests import iou3d_cases as C
 
 pytestmark = pytest.mark.gpu
 DEV = "cuda:0"
 
 
-def _boxes(rng, n, spread=20.0):
-    b = np.zeros((n, 7), np.float32)
-    b[:, :2] = rng.uniform(-spread, spread, (n, 2))
-    b[:, 2] = rng.uniform(-2, 0, n)
-    b[:, 3:6] = rng.uniform(0.6, 6.0, (n, 3))
-    b[:, 6] = rng.uniform(-6.5, 6.5, n)
-    return b
+_boxes = C.random_boxes
 
 
 def test_bev_overlap_iou_and_volume_iou_match_the_checker():
@@ -86,25 +82,67 @@ def test_rotate_iou_eval_mirror(criterion):
     assert rotate_iou_gpu_eval(q[:0], r, criterion).shape == (0, k)
 
 
-@pytest.mark.parametrize("n,thresh,pre,normal", [(1, 0.1, None, False), (63, 0.1, None, False), (64, 0.01, None, False),
-                                                 (65, 0.3, None, False), (700, 0.1, None, False),
-                                                 (4096, 0.2, 3000, False), (2500, 0.7, None, False),
-                                                 (900, 0.25, None, True)])
-def test_nms_matches_the_checker(n, thresh, pre, normal):
+def _nms_against_the_checker(n, nominal, pre, normal, spread=None):
+    """No pair may be ambiguous, so the keep lists must be EQUAL: the threshold is moved (by less than 0.01) into the
+    widest gap between oracle IoU values, the half-width of that gap exceeds the 1e-5 this file asserts for the IoU,
+    and (up to 4096 boxes, rotated) the GPU's IoU of every candidate pair is asserted within that 1e-5.  The threshold
+    reaches the kernel as a float32; its rounding (1e-8) is inside the margin."""
     from dfu3d_amd.pcdet_kitti import iou3d_nms_utils as U
-    rng = np.random.default_rng(100 + n)
-    boxes = _boxes(rng, n, 4.0 * np.sqrt(n) ** 0.5 + 4.0)
-    scores = rng.permutation(n).astype(np.float32) / n          # distinct -> the order is unambiguous
+    from dfu3d_amd import stages as st
+    boxes, scores = C.nms_scene(n, spread)
+    order = np.argsort(-scores.astype(np.float64), kind="stable")[:pre]
+    pairs = I.pair_ious(boxes[order], normal=normal)
+    thresh, half = I.widest_gap_threshold(pairs[2], nominal)
+    exp, _ = I.nms_sparse(boxes, scores, thresh, pre_maxsize=pre, normal=normal, pairs=pairs)
+    print("nms case n=%d pre=%s normal=%s: %d candidate pairs, threshold %.6f, half-width of its gap %.3g, oracle keeps %d"
+          % (n, pre, normal, pairs[0].size, thresh, half, len(exp)))
+    assert half > 1e-5 and abs(thresh - nominal) < 0.01, (thresh, half)        # on the oracle, before the GPU is touched
+    assert not (np.abs(pairs[2] - thresh) <= 1e-5).any()
+    if len(order) > 4096 or spread is not None:
+        assert 0.2 * len(order) < len(exp) < 0.8 * len(order), (len(exp), len(order))    # a trivial walk cannot pass
     tb, ts = torch.from_numpy(boxes).to(DEV), torch.from_numpy(scores).to(DEV)
+    if len(order) <= 4096 and not normal:
+        sb = torch.from_numpy(boxes[order]).to(DEV)
+        iou = st.boxes_bev(sb, sb, iou=True).cpu().numpy()
+        err = np.abs(iou[pairs[0], pairs[1]] - pairs[2])
+        print("  GPU IoU of the candidate pairs: worst |error| %.3g" % (err.max() if err.size else 0.0))
+        assert (err <= 1e-5).all(), err.max()
     if normal:
+        assert pre is None
         sel, _ = U.nms_normal_gpu(tb, ts, thresh)
     else:
         sel, _ = U.nms_gpu(tb, ts, thresh, pre_maxsize=pre)
-    exp, iou = I.nms(boxes, scores, thresh, pre_maxsize=pre, normal=normal)
     got = sel.cpu().numpy()
-    assert 0 < len(got) <= n
-    if not np.array_equal(got, exp):
-        # a pair whose IoU sits within float32 noise of the threshold may legitimately flip; anything else is a bug
-        near = np.abs(iou - thresh) < 1e-5
-        assert near.any(), (n, len(got), len(exp))
-        pytest.skip("keep lists differ only through a pair at the threshold (|iou - thresh| < 1e-5)")
+    assert got.dtype == np.int64 and 0 < len(got) <= n
+    assert np.array_equal(got, exp), (n, len(got), len(exp), int((got[:min(len(got), len(exp))] != exp[:min(len(got), len(exp))]).argmax()))
+
+
+@pytest.mark.parametrize("n,thresh,pre,normal", C.NMS_CASES)
+def test_nms_matches_the_checker(n, thresh, pre, normal):
+    _nms_against_the_checker(n, thresh, pre, normal)
+
+
+def test_nms_dense_scene_at_a_high_threshold():
+    """2500 boxes on 4 m x 4 m at 0.7: a third is suppressed (the 2500-box case above keeps 99.5 %)."""
+    n, nominal, spread = C.DENSE_2500
+    _nms_against_the_checker(n, nominal, None, False, spread=spread)
+
+
+def test_nms_more_boxes_than_the_abi_admits():
+    """32769 boxes: DFU3D_ERANGE, as an exception from the wrapper and with `keep` / `num_keep` untouched at the C ABI."""
+    import ctypes
+    from dfu3d_amd import _lib, stages as st
+    n = 32769
+    boxes = torch.from_numpy(C.random_boxes(np.random.default_rng(3), n, 200.0)).to(DEV)
+    for normal in (False, True):
+        with pytest.raises(_lib.Dfu3dError, match=r"\(-3\)"):
+            st.nms_bev(boxes, 0.2, normal=normal)
+        keep = torch.full((n,), -1, dtype=torch.int64, device=DEV)
+        num = torch.full((1,), -7, dtype=torch.int32, device=DEV)
+        mask = torch.zeros(64, dtype=torch.int64, device=DEV)         # never touched: the size check comes first
+        fn = _lib.lib().dfu3d_nms_normal_bev if normal else _lib.lib().dfu3d_nms_bev
+        rc = fn(ctypes.c_void_p(boxes.data_ptr()), n, ctypes.c_float(0.2), ctypes.c_void_p(mask.data_ptr()),
+                ctypes.c_void_p(keep.data_ptr()), ctypes.c_void_p(num.data_ptr()), st._stream())
+        torch.cuda.synchronize()
+        assert rc == -3                                                # DFU3D_ERANGE
+        assert int(num.item()) == -7 and bool((keep == -1).all()) and not bool(mask.any())

@@ -147,3 +147,65 @@ def test_reference_margin_semantics_how_often_a_suppression_decision_differs():
         assert flips <= 0.01 * n, (thr, flips)
     print("reference-margin vs exact overlap: worst |dIoU| %.4f over %d pairs; (kept, keep-list flips, pair flips) per threshold: %s"
           % (worst, len(ref), report))
+
+
+def test_a_box_without_area_overlaps_nothing():
+    """A point or a segment as the CLIPPING box: its zero-length edges give no half-plane, the result is still 0."""
+    A = np.array([[0, 0, 0, 4, 2, 1.5, 0.3]])
+    for dx, dy in ((0, 0), (0, 1), (1, 0)):
+        Z = np.array([[0.1, 0.1, 0, dx, dy, 1.5, 0.7]])
+        assert I.boxes_bev(A, Z, iou=False)[0, 0] == 0.0 and I.boxes_bev(Z, A, iou=False)[0, 0] == 0.0
+        assert I.boxes_bev(A, Z)[0, 0] == 0.0 and I.boxes_bev(Z, Z)[0, 0] == 0.0
+
+
+def test_sparse_nms_is_the_dense_one():
+    """`nms_sparse` / `pair_ious` (no n x n matrix) against the dense `nms`: the same keep list and, pair by pair, the
+    same float64 IoU; every pair the sparse list leaves out is exactly 0 in the dense matrix."""
+    from tests import iou3d_cases as C
+    for n, thresh, pre, normal in ((2000, 0.2, None, False), (2100, 0.3, 1500, False), (1900, 0.25, None, True),
+                                   (1, 0.1, None, False), (2, 0.1, 5, True)):
+        boxes = C.random_boxes(np.random.default_rng(n), n, 4.0 * n ** 0.25 + 4.0)
+        scores = np.random.default_rng(n + 1).permutation(n).astype(np.float32)
+        keep_d, iou_d = I.nms(boxes, scores, thresh, pre_maxsize=pre, normal=normal)
+        keep_s, (i, j, iou_s) = I.nms_sparse(boxes, scores, thresh, pre_maxsize=pre, normal=normal)
+        assert np.array_equal(keep_d, keep_s) and keep_s.dtype == keep_d.dtype
+        assert (j > i).all() and np.array_equal(iou_s, iou_d[i, j])
+        assert (np.diff(i) >= 0).all() and ((np.diff(i) > 0) | (np.diff(j) > 0)).all()      # sorted, no pair twice
+        rest = np.triu(iou_d, 1)
+        rest[i, j] = 0.0
+        assert not rest.any()
+        if n >= 1900:
+            assert 0.2 * len(iou_d) < len(keep_d) < 0.8 * len(iou_d) and (iou_s > thresh).sum() > 500
+            # a second threshold walked over the same pair list
+            keep_2, _ = I.nms_sparse(boxes, scores, 0.5, pre_maxsize=pre, normal=normal, pairs=(i, j, iou_s))
+            assert np.array_equal(keep_2, I.nms(boxes, scores, 0.5, pre_maxsize=pre, normal=normal, iou=iou_d)[0])
+
+
+def test_widest_gap_threshold():
+    thr, half = I.widest_gap_threshold([0.1, 0.195, 0.197, 0.204, 0.2045, 0.3], 0.2)
+    assert abs(thr - 0.2005) < 1e-12 and abs(half - 0.0035) < 1e-12
+    thr, half = I.widest_gap_threshold([], 0.2)                      # nothing in the window: its two ends bound the gap
+    assert abs(thr - 0.2) < 1e-12 and abs(half - 0.01) < 1e-12
+    thr, half = I.widest_gap_threshold([0.2], 0.2)                   # never ON a value
+    assert abs(abs(thr - 0.2) - 0.005) < 1e-12 and abs(half - 0.005) < 1e-12
+
+
+def test_the_gpu_nms_cases_have_no_pair_near_their_threshold():
+    """What tests/test_gpu_iou3d.py relies on, on the oracle alone: every case's threshold sits in a gap whose
+    half-width exceeds the 1e-5 the GPU IoU is asserted to, and the cases with more than 4096 boxes suppress a real
+    share.  (The 4 m x 4 m case of 2500 boxes is asserted in the GPU test only: it has 3e6 overlapping pairs.)"""
+    from tests import iou3d_cases as C
+    seen = {}
+    for n, nominal, pre, normal in C.NMS_CASES:
+        boxes, scores = C.nms_scene(n)
+        order = np.argsort(-scores.astype(np.float64), kind="stable")[:pre]
+        pairs = I.pair_ious(boxes[order], normal=normal)
+        thr, half = I.widest_gap_threshold(pairs[2], nominal)
+        assert half > 1e-5 and abs(thr - nominal) < 0.01, (n, thr, half)
+        assert not (np.abs(pairs[2] - thr) < half * (1 - 1e-9)).any()
+        keep, _ = I.nms_sparse(boxes, scores, thr, pre, normal, pairs=pairs)
+        seen[(n, nominal, pre, normal)] = (round(thr, 6), half, len(keep))
+        if n > 4096:
+            assert 0.2 * len(order) < len(keep) < 0.8 * len(order), (n, len(keep))
+    print("NMS cases (threshold, half-width of its gap, kept):", seen)
+    assert seen[(4096, 0.2, 3000, False)][0] == 0.20584
