@@ -84,6 +84,8 @@ VARIANTS = {
     "no_mid": ["-DDFU3D_DBG_NO_MID"],
     # cycles between the DBG_T marks of a kernel, summed over its workgroups (tools/p1_timing.py)
     "timing": ["-DDFU3D_DBG_TIMING"],
+    # every kernel launch counted on the host (dfu3d_debug_launch_count): the launch-count test of the chain
+    "count": ["-DDFU3D_DBG_COUNT_LAUNCHES"],
     # the HOST side of the C ABI (argument validation, geometry, workspace carve-up) under AddressSanitizer +
     # UndefinedBehaviorSanitizer; device code as in the product.  CPU only (tools/sanitize_cpu.sh): GPU ASan is not available
     "asan_host": ["-O1", "-g", "-Xarch_host", "-fsanitize=address", "-Xarch_host", "-fsanitize=undefined",

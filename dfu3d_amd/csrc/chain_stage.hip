@@ -173,6 +173,9 @@ extern "C" int dfu3d_chain_workspace_init(const dfu3d_chain_cfg *cfg, void *work
   if (cfg->dense) {
     const int rc = dfu3d_bin_table_init(w.table, (int64_t)cfg->V * w.table_entries, stream);
     if (rc) return rc;
+    const int rt = dfu3d_bp_tables_forget(w.blk_cnt, cfg->V, cfg->H, cfg->W, cfg->cap_vox, cfg->geom.max_points_per_voxel,
+                                          w.table_entries, stream);
+    if (rt) return rt;
   }
   hipLaunchKernelGGL(k_fill_i32, dim3((cfg->V * cfg->max_inst + 255) / 256), dim3(256), 0,
                      (hipStream_t)stream, cfg->V * cfg->max_inst, 1, w.stat_enable);
@@ -204,9 +207,14 @@ extern "C" int dfu3d_pseudo_boxes(
   carve(cfg, (char *)workspace, &w);
   hipStream_t st = (hipStream_t)stream;
   const int V = cfg->V, M = cfg->max_inst, S = V * M, cap_n = cfg->cap_n;
-  // (one small kernel, not three memsets: common.hpp, k_fill_words)
-  if (dfu3d_fill_small_async(n_rows, sizeof(int32_t), status, sizeof(uint32_t), w.pool_cursor, sizeof(int64_t), st) != hipSuccess)
+  // (one kernel, not three memsets: common.hpp, k_fill_words; with the dense path the same launch zeroes the words the
+  // back-projection starts from)
+  if (cfg->dense) {
+    CHAIN_TRY(dfu3d_bp_clear_chain(w.blk_cnt, V, cfg->H, cfg->W, w.table_entries, n_rows, sizeof(int32_t), status,
+                                   sizeof(uint32_t), w.pool_cursor, sizeof(int64_t), stream));
+  } else if (dfu3d_fill_small_async(n_rows, sizeof(int32_t), status, sizeof(uint32_t), w.pool_cursor, sizeof(int64_t), st) != hipSuccess) {
     return DFU3D_ELAUNCH;
+  }
   // a4
   if (cfg->apply_fov) {
     CHAIN_TRY(dfu3d_fov_filter(points, pt_off, view_frame, calib, V, cfg->fov_h, cfg->fov_w, cap_n,
@@ -231,9 +239,9 @@ extern "C" int dfu3d_pseudo_boxes(
                                 w.ib_pix, w.n_ag, w.K, w.a_bits, w.a_x, w.a_y, w.a_z, stream));
   // a7-a9
   if (cfg->dense) {
-    CHAIN_TRY(dfu3d_backproject_bin(depth, calib, masks, cfg->mask_format, n_inst, V, M, cfg->H, cfg->W, &cfg->geom, 1, w.table,
-                                    w.pix_bin, w.blk_cnt, cfg->cap_vox, w.n_vox, w.vox_pix, w.b_bits, w.b_x,
-                                    w.b_y, w.b_z, status, DFU3D_BP_ALL, stream));
+    CHAIN_TRY(dfu3d_backproject_bin_chain(depth, calib, masks, cfg->mask_format, n_inst, V, M, cfg->H, cfg->W, &cfg->geom, 1,
+                                          w.table, w.pix_bin, w.blk_cnt, cfg->cap_vox, w.n_vox, w.vox_pix, w.b_bits, w.b_x,
+                                          w.b_y, w.b_z, status, stream));
   } else {
     if (dfu3d_fill_async(w.n_vox, 0, sizeof(int32_t) * V, st) != hipSuccess) return DFU3D_ELAUNCH;
   }
@@ -278,3 +286,12 @@ extern "C" int dfu3d_pseudo_boxes(
                              stream));
   return DFU3D_OK;
 }
+
+#ifdef DFU3D_DBG_COUNT_LAUNCHES
+long long g_dbg_launches = 0;
+extern "C" long long dfu3d_debug_launch_count(int reset) {
+  const long long n = g_dbg_launches;
+  if (reset) g_dbg_launches = 0;
+  return n;
+}
+#endif

@@ -8,7 +8,10 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include <stddef.h>
+#include <string.h>
 #include "dfu3d.h"
+#include "dbg.hpp"
 
 #define DFU3D_WAVE 64
 
@@ -359,3 +362,20 @@ static inline hipError_t dfu3d_fill_small_async(void *a, size_t bytes_a, void *b
                      (uint32_t *)c, (int)(bytes_c / 4), 0u);
   return hipGetLastError();
 }
+
+// ---- internal to the library: the chain's forms of the back-projection stage (pixel_stage.hip), called by
+// dfu3d_pseudo_boxes / dfu3d_chain_workspace_init only.  dfu3d_backproject_bin_chain = dfu3d_backproject_bin with
+// DFU3D_BP_ALL, the same results in n_vox and in every voxel record a later stage of the chain reads, with the work the
+// chain does not need left out: the edge tables are kept in blk_cnt across calls (rebuilt when the geometry differs),
+// a voxel under no mask stores its it_bits only, the repair is one launch, and the zeroing is the caller's
+// (dfu3d_bp_clear_chain, before the first kernel of the chain).
+int dfu3d_backproject_bin_chain(
+    const float *depth, const float *calib, const void *masks, int32_t mask_format, const int32_t *n_inst,
+    int32_t V, int32_t max_inst, int32_t H, int32_t W, const dfu3d_bin_geom *geom,
+    int32_t key_axis, void *table, uint32_t *pix_bin, int32_t *blk_cnt, int32_t cap_vox,
+    int32_t *n_vox, uint32_t *vox_pix, uint32_t *it_bits, double *it_x, double *it_y,
+    double *it_z, uint32_t *status, void *stream);
+int dfu3d_bp_clear_chain(int32_t *blk_cnt, int32_t V, int32_t H, int32_t W, int64_t table_entries, void *a, size_t bytes_a,
+                         void *b, size_t bytes_b, void *c, size_t bytes_c, void *stream);
+int dfu3d_bp_tables_forget(int32_t *blk_cnt, int32_t V, int32_t H, int32_t W, int32_t cap_vox, int32_t max_points,
+                           int64_t table_entries, void *stream);

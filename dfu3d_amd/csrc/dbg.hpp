@@ -10,6 +10,8 @@
 //                                every source file that uses the marks has its own counters and exports a reader with
 //                                DBG_T_READER(name) (pixel_stage.hip: dfu3d_debug_timing_pixel; tools/p1_timing.py).
 //                                Same results as the product.
+//   DFU3D_DBG_COUNT_LAUNCHES     test build: every kernel launch of the library counts itself on the host;
+//                                dfu3d_debug_launch_count(reset) (chain_stage.hip) reads the counter.  Same results as the product.
 #pragma once
 
 #ifdef DFU3D_DBG_COMBO_KEYBITS
@@ -50,4 +52,10 @@ static __device__ unsigned long long g_dbg_cycles[DBG_T_SLOTS];
 #define DBG_T_ADD(k, v) do {} while (0)
 #define DBG_T_MAX(k, v) do {} while (0)
 #define DBG_T_READER(name)
+#endif
+
+#ifdef DFU3D_DBG_COUNT_LAUNCHES
+extern long long g_dbg_launches;                   // (host; defined in chain_stage.hip)
+#undef hipLaunchKernelGGL
+#define hipLaunchKernelGGL(kernelName, ...) do { ++g_dbg_launches; hipLaunchKernelGGLInternal((kernelName), __VA_ARGS__); } while (0)
 #endif

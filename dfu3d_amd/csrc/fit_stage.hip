@@ -789,30 +789,12 @@ __global__ __launch_bounds__(TCT, (NC <= GRID_NC_SMALL ? 8 : 4)) void k_range_cl
   }
 }
 
-__global__ __launch_bounds__(CT) void k_range_cluster_small(
-    const double *__restrict__ px, const double *__restrict__ py,
-    const long long *__restrict__ seg_base, const int *__restrict__ seg_cnt, double R0,
-    double Rd, int *__restrict__ label, double *__restrict__ sx, double *__restrict__ sy,
-    int *__restrict__ si, long long pool_cap) {
-  __shared__ __attribute__((aligned(16))) int s_parent[SMALL_N];
-  __shared__ int s_summ[SMALL_N / GRP];
-  __shared__ float4 s_box[SMALL_N / GRP];
-  __shared__ int s_summ2[SMALL_N / GRP / BLK];
-  __shared__ float4 s_box2[SMALL_N / GRP / BLK];
-  __shared__ double s_red[4 * (CT / 64)];
-  __shared__ int s_w[CT / 64];
-  const int s = blockIdx.x;
-  const int n = seg_cnt[s];
-  if (n == 0 || n > SMALL_N) return;
-  const long long base = seg_base[s];
-  if (si[2 * pool_cap + base]) return;                 // a grid variant did it (mark written there)
-  cell_sort<SMALL_N>(px + base, py + base, n, s_parent, s_red, s_w, sx + base, sy + base, si + base);
-  ParI par{s_parent, false};
-  cluster_body<ParI, SMALL_N / GRP>(par, s_summ, s_box, s_summ2, s_box2, s_red, sx + base, sy + base,
-                                    n, R0, Rd, si + base, si + pool_cap + base, label + base);
-}
-
-__global__ __launch_bounds__(CT) void k_range_cluster_large(
+// Fallback for the instances no grid variant took (wider than the largest grid): point-level union-find, ONE launch for
+// both footprints -- a workgroup reads its segment's size and takes the form that fits it: up to SMALL_N points 32-bit
+// parents, up to LARGE_N 16-bit parents in LDS, beyond that parents in global memory.  (Two kernels until round 6, each
+// leaving at once for the segments of the other -- which is every segment of an ordinary pass: a launch of S workgroups
+// for nothing.  The small form now sits in the first 16 KB of the large form's arrays; its results are the same.)
+__global__ __launch_bounds__(CT) void k_range_cluster_fallback(
     const double *__restrict__ px, const double *__restrict__ py,
     const long long *__restrict__ seg_base, const int *__restrict__ seg_cnt, double R0,
     double Rd, int *__restrict__ label, double *__restrict__ sx, double *__restrict__ sy,
@@ -824,11 +806,19 @@ __global__ __launch_bounds__(CT) void k_range_cluster_large(
   __shared__ float4 s_box2[LARGE_GRP / BLK];
   __shared__ double s_red[4 * (CT / 64)];
   __shared__ int s_w[CT / 64];
+  static_assert(sizeof(int) * SMALL_N <= sizeof(unsigned short) * LARGE_N && SMALL_N / GRP <= LARGE_GRP, "the small form fits");
   const int s = blockIdx.x;
   const int n = seg_cnt[s];
-  if (n <= SMALL_N) return;
+  if (n == 0) return;
   const long long base = seg_base[s];
   if (si[2 * pool_cap + base]) return;                 // a grid variant did it (mark written there)
+  if (n <= SMALL_N) {
+    cell_sort<SMALL_N>(px + base, py + base, n, (int *)s_parent, s_red, s_w, sx + base, sy + base, si + base);
+    ParI par{(int *)s_parent, false};
+    cluster_body<ParI, SMALL_N / GRP>(par, s_summ, s_box, s_summ2, s_box2, s_red, sx + base, sy + base,
+                                      n, R0, Rd, si + base, si + pool_cap + base, label + base);
+    return;
+  }
   cell_sort<LARGE_N / 2>(px + base, py + base, n, (int *)s_parent, s_red, s_w, sx + base, sy + base,
                          si + base);
   if (n <= LARGE_N) {
@@ -1714,12 +1704,8 @@ extern "C" int dfu3d_range_cluster(const double *px, const double *py, const int
                      label, sx, sy, si, (long long)pool_cap, 0, 0x7FFFFFFF);
   DFU3D_LAUNCH_CHECK();
   // fallback for instances wider than the largest grid: point-level union-find
-  // (two LDS footprints; each kernel returns at once for segments it does not own)
-  hipLaunchKernelGGL(k_range_cluster_small, dim3(S), dim3(CT), 0, (hipStream_t)stream, px, py,
-                     (const long long *)seg_base, seg_cnt, R0, Rd, label, sx, sy, si,
-                     (long long)pool_cap);
-  DFU3D_LAUNCH_CHECK();
-  hipLaunchKernelGGL(k_range_cluster_large, dim3(S), dim3(CT), 0, (hipStream_t)stream, px, py,
+  // (one launch, the LDS footprint chosen by the segment's size; it returns at once for segments a grid variant did)
+  hipLaunchKernelGGL(k_range_cluster_fallback, dim3(S), dim3(CT), 0, (hipStream_t)stream, px, py,
                      (const long long *)seg_base, seg_cnt, R0, Rd, label, sx, sy, si,
                      (long long)pool_cap);
   DFU3D_LAUNCH_CHECK();

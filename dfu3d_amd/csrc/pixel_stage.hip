@@ -285,10 +285,8 @@ __device__ __forceinline__ const double *edge_tab_p(const float2 *tab, const Fas
 inline int tables_threads(const FastGeom &fg, const dfu3d_bin_geom &g) {
   return fg.tJ + fg.pJ + 4 + (fg.mid_ok ? g.t_n + g.p_n + 2 : 0);
 }
-__global__ void k_bp_tables(dfu3d_bin_geom g, FastGeom fg, float2 *__restrict__ tab, BinCold *__restrict__ cold) {
-  const int i = blockIdx.x * blockDim.x + threadIdx.x;
+__device__ __forceinline__ void tables_entry(int i, const dfu3d_bin_geom &g, const FastGeom &fg, float2 *__restrict__ tab) {
   const double pi = 3.14159265358979323846;
-  if (i == 0 && cold) { cold->g = g; cold->fg = fg; }      // (k_bp_bin's copy of the records)
   if (i >= fg.tJ + fg.pJ + 4) {
     // tier 1.5 (pixel_bin_mid): edge k of the window in the space the fp64 test works in -- -cos(B) for theta,
     // tan(B) for phi (B = rmin + k * vsize as the reference's floor((angle - rmin) / vsize) implies it)
@@ -330,6 +328,11 @@ __global__ void k_bp_tables(dfu3d_bin_geom g, FastGeom fg, float2 *__restrict__ 
   const bool ok = (edge(kn) <= c) && (c < edge(kn + 1)) && others >= (0.5 + TAB_SLOP_W) * w + 1.001 * (double)TAB_DMAX;
   tab[i] = ok ? make_float2((float)edge(k1), __int_as_float((int)k1)) : make_float2(__int_as_float(0x7FC00000), __int_as_float(0));
 }
+__global__ void k_bp_tables(dfu3d_bin_geom g, FastGeom fg, float2 *__restrict__ tab, BinCold *__restrict__ cold) {
+  const int i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i == 0 && cold) { cold->g = g; cold->fg = fg; }      // (k_bp_bin's copy of the records)
+  tables_entry(i, g, fg, tab);
+}
 
 // bin of q from the axis' table; false = undecided (no branches: garbage in -- NaN, an index off the table -- meets
 // a NaN entry and fails the comparison).  The index is clamped as an unsigned number: a negative one lands on the upper
@@ -365,8 +368,7 @@ __device__ __forceinline__ Recip recip_of(const FastCal &f) {
   return r;
 }
 
-__global__ void k_bp_prep(const ViewCalib *__restrict__ calib, int V, int H, int W, FastCal *__restrict__ out) {
-  const int v = blockIdx.x * blockDim.x + threadIdx.x;
+__device__ __forceinline__ void prep_view(int v, const ViewCalib *__restrict__ calib, int V, int H, int W, FastCal *__restrict__ out) {
   if (v >= V) return;
   const ViewCalib c = calib[v];
   FastCal f;
@@ -387,6 +389,61 @@ __global__ void k_bp_prep(const ViewCalib *__restrict__ calib, int V, int H, int
   const Recip r = make_recip(c);
   f.rfu = r.rfu; f.rfv = r.rfv;
   out[v] = f;
+}
+__global__ void k_bp_prep(const ViewCalib *__restrict__ calib, int V, int H, int W, FastCal *__restrict__ out) {
+  prep_view(blockIdx.x * blockDim.x + threadIdx.x, calib, V, H, W, out);
+}
+
+// The chain's form of k_bp_prep + k_bp_tables: ONE launch, and the tables -- functions of the geometry records alone --
+// are built only when the records differ from the ones the scratch's tables were built from.  The tag is BinCold itself
+// (k_bp_bin's copy of dfu3d_bin_geom and FastGeom, next to the tables in the same scratch): the table workgroups compare
+// it word by word with the records of this call and leave when they agree.  When they differ every table workgroup
+// builds its entries, and the LAST one to finish (a counter behind the tables) writes the new records -- after every
+// workgroup has read the old ones, so no workgroup of the launch can see a tag that is half old, half new.  Calls on one
+// scratch are stream-ordered; dfu3d_bp_tables_forget() makes a fresh scratch's tag invalid.
+constexpr int PTB = 256;
+__global__ __launch_bounds__(PTB) void k_bp_prep_tables(const ViewCalib *__restrict__ calib, int V, int H, int W,
+                                                        FastCal *__restrict__ out, int prep_blocks, int tab_blocks,
+                                                        BinCold want, float2 *__restrict__ tab, BinCold *cold, int *tab_done) {
+  if ((int)blockIdx.x < prep_blocks) {
+    prep_view(blockIdx.x * PTB + threadIdx.x, calib, V, H, W, out);
+    return;
+  }
+  static_assert(sizeof(BinCold) % 4 == 0, "BinCold: compared as words");
+  const uint32_t *have = (const uint32_t *)cold, *w = (const uint32_t *)&want;
+  bool same = true;
+  for (int k = 0; k < (int)(sizeof(BinCold) / 4); k++) same = same && (have[k] == w[k]);
+  if (same) return;                                  // the usual case: the geometry of the call before
+  tables_entry((blockIdx.x - prep_blocks) * PTB + threadIdx.x, want.g, want.fg, tab);
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    __threadfence();
+    if (atomicAdd(tab_done, 1) == tab_blocks - 1) {
+      *cold = want;
+      *tab_done = 0;
+    }
+  }
+}
+// k_fill_words (common.hpp) of zeros, whose first workgroup also zeroes three small regions
+__global__ __launch_bounds__(256) void k_fill_words_and_small(uint32_t *__restrict__ p, size_t n, uint32_t *a, int na,
+                                                              uint32_t *b, int nb, uint32_t *c, int nc) {
+  const size_t head = ((16u - (unsigned)((uintptr_t)p & 15u)) & 15u) / 4u < n ? ((16u - (unsigned)((uintptr_t)p & 15u)) & 15u) / 4u : n;
+  uint4 *q = (uint4 *)(p + head);                      // the body in 16-byte stores
+  const size_t nq = (n - head) / 4;
+  const size_t tid = (size_t)blockIdx.x * 256 + threadIdx.x, nth = (size_t)gridDim.x * 256;
+  for (size_t i = tid; i < nq; i += nth) q[i] = make_uint4(0u, 0u, 0u, 0u);
+  const size_t done = head + nq * 4;
+  if (tid < head) p[tid] = 0u;
+  if (tid < n - done) p[done + tid] = 0u;
+  if (blockIdx.x == 0) {
+    for (int i = threadIdx.x; i < na; i += 256) a[i] = 0u;
+    for (int i = threadIdx.x; i < nb; i += 256) b[i] = 0u;
+    for (int i = threadIdx.x; i < nc; i += 256) c[i] = 0u;
+  }
+}
+__global__ void k_bp_tables_forget(BinCold *cold, int *tab_done) {
+  if (threadIdx.x < sizeof(BinCold) / 4) ((uint32_t *)cold)[threadIdx.x] = 0xFFFFFFFFu;   // (t_n = -1: no geometry passes cfg checks with it)
+  if (threadIdx.x == 0) *tab_done = 0;
 }
 
 __device__ __forceinline__ void backproject_f32(const FastCal &fc, int col, int row, float d, float &xf, float &yf,
@@ -895,12 +952,14 @@ struct VoxOut {
 
 __device__ __forceinline__ void emit_voxel(const VoxOut &o, size_t at, const ViewCalib &c, const Recip &rc,
                                            const float *depth_v, int W, uint32_t pix, const void *masks,
-                                           int mask_format, int m, int max_inst, int HW, int v) {
+                                           int mask_format, int m, int max_inst, int HW, int v, bool lean) {
   const int row = (int)pix / W, col = (int)pix - row * W;
   double x, y, z;
   pixel_to_lidar(c, rc, col, row, depth_v[pix], x, y, z);
+  const uint32_t bits = masks ? mask_bits_at(masks, mask_format, v, max_inst, m, HW, (int)pix) : 0u;
+  o.it_bits[at] = bits;
+  if (lean && bits == 0u) return;                   // (LEAN of k_bp_vox)
   o.vox_pix[at] = pix;
-  o.it_bits[at] = masks ? mask_bits_at(masks, mask_format, v, max_inst, m, HW, (int)pix) : 0u;
   o.it_x[at] = x;
   o.it_y[at] = y;
   o.it_z[at] = z;
@@ -929,6 +988,11 @@ struct VoxWalk {
   const uint32_t *bitmap, *wpre;
   int NSEG, BW, NJ, tiles_x;
 };
+// LEAN (the chain, where the voxel planes are workspace and the segment build is their only reader): a voxel under no
+// instance mask stores its it_bits (0) and nothing else -- k_seg_count reads the bits alone and k_seg_write loads the
+// coordinates of an item only under one of its bits, so the pixel and the three fp64 coordinates of such a voxel (28 of
+// its 32 bytes, scattered by rank) are never read.  Ranks, n_vox and the table reset do not depend on the stores.
+template <bool LEAN>
 __global__ __launch_bounds__(VXB) void k_bp_vox(
     const float *__restrict__ depth, const ViewCalib *__restrict__ calib, const void *__restrict__ masks, int mask_format,
     const int *__restrict__ n_inst, int max_inst, int W, int HW, int64_t E_view, void *table, int64_t E_total, int cap_vox,
@@ -998,11 +1062,13 @@ __global__ __launch_bounds__(VXB) void k_bp_vox(
         keep = true;
       } else if (k < max_voxels) {
         const size_t at = (size_t)v * cap_vox + k;
-        out.vox_pix[at] = pix;
         out.it_bits[at] = m_bits;
-        out.it_x[at] = x;
-        out.it_y[at] = yy;
-        out.it_z[at] = z;
+        if (!LEAN || m_bits != 0u) {
+          out.vox_pix[at] = pix;
+          out.it_x[at] = x;
+          out.it_y[at] = yy;
+          out.it_z[at] = z;
+        }
       }
     }
     if (!keep) {                                    // (rep is only ever written by the repair)
@@ -1015,31 +1081,37 @@ __global__ __launch_bounds__(VXB) void k_bp_vox(
 }
 
 // ---- O1: bin id per pixel, exact classification, only for views with a repair queue ----
-__global__ __launch_bounds__(PB) void k_bp_rebin(
-    const float *__restrict__ depth, const ViewCalib *__restrict__ calib, dfu3d_bin_geom g, int W, int HW,
+// (The phases of the repair are device functions of (v, bx, gx) -- the view, this workgroup's index among the gx
+// workgroups that share the view's work with the grid's stride: the stage-by-stage entry point runs each as a kernel of
+// its own, a few workgroups per view; the chain runs all of them in ONE kernel, k_bp_repair, a workgroup per view.)
+__device__ __forceinline__ void ph_rebin(int v, int bx, int gx,
+    const float *__restrict__ depth, const ViewCalib *__restrict__ calib, const dfu3d_bin_geom &g, int W, int HW,
     int key_axis, const int *__restrict__ n_q, uint32_t *__restrict__ pix_bin) {
-  const int v = blockIdx.y;
   if (n_q[v] == 0) return;                           // the usual case
   const ViewCalib c = calib[v];
   const Recip rc = make_recip(c);
   bool rerr = false;
-  for (int pix = blockIdx.x * PB + threadIdx.x; pix < HW; pix += gridDim.x * PB) {
+  for (int pix = bx * PB + threadIdx.x; pix < HW; pix += gx * PB) {
     double key;
     pix_bin[(size_t)v * HW + pix] = pixel_bin(c, rc, g, W, pix, depth[(size_t)v * HW + pix], key_axis, key, rerr);
   }
 }
+__global__ __launch_bounds__(PB) void k_bp_rebin(
+    const float *__restrict__ depth, const ViewCalib *__restrict__ calib, dfu3d_bin_geom g, int W, int HW,
+    int key_axis, const int *__restrict__ n_q, uint32_t *__restrict__ pix_bin) {
+  ph_rebin(blockIdx.y, blockIdx.x, gridDim.x, depth, calib, g, W, HW, key_axis, n_q, pix_bin);
+}
 
 // ---- O2: allocate a pixel list per queued bin ----------------------------------
 // rep[e] <- list base, cnt[e] <- OVF_FLAG | 0 (fill cursor), q_cnt <- count
-__global__ void k_ovf_alloc(void *table, int64_t E_total, int64_t E_view, int cap_q,
+__device__ __forceinline__ void ph_ovf_alloc(int v, int bx, int gx, void *table, int64_t E_total, int64_t E_view, int cap_q,
                             const uint32_t *__restrict__ q_bins,
                             const int *__restrict__ n_q, int *__restrict__ q_cnt,
                             int *__restrict__ q_cursor, int HW,
                             uint32_t *__restrict__ status) {
-  const int v = blockIdx.y;
   const int no = min(n_q[v], cap_q);
   const Table T = table_view(table, E_total);
-  for (int s = blockIdx.x * blockDim.x + threadIdx.x; s < no; s += gridDim.x * blockDim.x) {
+  for (int s = bx * blockDim.x + threadIdx.x; s < no; s += gx * blockDim.x) {
     const int64_t e = (int64_t)v * E_view + q_bins[(size_t)v * cap_q + s];
     const int c = (int)T.cnt[e];
     const int off = atomicAdd(&q_cursor[v], c);
@@ -1049,15 +1121,19 @@ __global__ void k_ovf_alloc(void *table, int64_t E_total, int64_t E_view, int ca
     T.cnt[e] = OVF_FLAG;
   }
 }
+__global__ void k_ovf_alloc(void *table, int64_t E_total, int64_t E_view, int cap_q, const uint32_t *__restrict__ q_bins,
+                            const int *__restrict__ n_q, int *__restrict__ q_cnt, int *__restrict__ q_cursor, int HW,
+                            uint32_t *__restrict__ status) {
+  ph_ovf_alloc(blockIdx.y, blockIdx.x, gridDim.x, table, E_total, E_view, cap_q, q_bins, n_q, q_cnt, q_cursor, HW, status);
+}
 
 // ---- O3: gather the pixel indices of queued bins -------------------------------
-__global__ __launch_bounds__(PB) void k_ovf_gather(
+__device__ __forceinline__ void ph_ovf_gather(int v, int bx, int gx,
     const uint32_t *__restrict__ pix_bin, void *table, int64_t E_total, int64_t E_view,
     int HW, const int *__restrict__ n_q, uint32_t *__restrict__ q_list) {
-  const int v = blockIdx.y;
   if (n_q[v] == 0) return;                         // the usual case: a few workgroups per view leave at once
   const Table T = table_view(table, E_total);
-  for (int base = blockIdx.x * PBLK + threadIdx.x * PPT; base < HW; base += gridDim.x * PBLK) {
+  for (int base = bx * PBLK + threadIdx.x * PPT; base < HW; base += gx * PBLK) {
     for (int k = 0; k < PPT; k++) {
       const int pix = base + k;
       if (pix >= HW) break;
@@ -1071,9 +1147,14 @@ __global__ __launch_bounds__(PB) void k_ovf_gather(
     }
   }
 }
+__global__ __launch_bounds__(PB) void k_ovf_gather(
+    const uint32_t *__restrict__ pix_bin, void *table, int64_t E_total, int64_t E_view,
+    int HW, const int *__restrict__ n_q, uint32_t *__restrict__ q_list) {
+  ph_ovf_gather(blockIdx.y, blockIdx.x, gridDim.x, pix_bin, table, E_total, E_view, HW, n_q, q_list);
+}
 
 // ---- O4: per overflow bin, T = max_points-th smallest pixel, kmin over pix<=T -
-__global__ __launch_bounds__(256) void k_ovf_select(
+__device__ __forceinline__ void ph_ovf_select(int v, int bx, int gx,
     const float *__restrict__ depth, const ViewCalib *__restrict__ calib, int W, int HW,
     int key_axis, int max_points, void *table, int64_t E_total, int64_t E_view,
     int cap_ovf, const uint32_t *__restrict__ ovf_bins, const int *__restrict__ n_ovf,
@@ -1081,12 +1162,11 @@ __global__ __launch_bounds__(256) void k_ovf_select(
   __shared__ int hist[256];
   __shared__ uint32_t s_sel[2];
   __shared__ unsigned long long s_min[4];
-  const int v = blockIdx.y;
   const int no = min(n_ovf[v], cap_ovf);
   const Table T = table_view(table, E_total);
   const ViewCalib c = calib[v];
   const Recip rc = make_recip(c);
-  for (int s = blockIdx.x; s < no; s += gridDim.x) {     // uniform per block
+  for (int s = bx; s < no; s += gx) {     // uniform per block
   const int64_t e = (int64_t)v * E_view + ovf_bins[(size_t)v * cap_ovf + s];
   const int n = ovf_cnt[(size_t)v * cap_ovf + s];
   const uint32_t *lst = ovf_list + (size_t)v * HW + T.rep[e];
@@ -1160,26 +1240,33 @@ __global__ __launch_bounds__(256) void k_ovf_select(
   }
   }
 }
+__global__ __launch_bounds__(256) void k_ovf_select(
+    const float *__restrict__ depth, const ViewCalib *__restrict__ calib, int W, int HW,
+    int key_axis, int max_points, void *table, int64_t E_total, int64_t E_view,
+    int cap_ovf, const uint32_t *__restrict__ ovf_bins, const int *__restrict__ n_ovf,
+    const int *__restrict__ ovf_cnt, const uint32_t *__restrict__ ovf_list) {
+  ph_ovf_select(blockIdx.y, blockIdx.x, gridDim.x, depth, calib, W, HW, key_axis, max_points, table, E_total, E_view,
+                cap_ovf, ovf_bins, n_ovf, ovf_cnt, ovf_list);
+}
 
 // ---- O5: outputs of the repaired bins ---------------------------------------------
-__global__ __launch_bounds__(256) void k_bp_fix(
+__device__ __forceinline__ void ph_fix(int v, int bx, int gx, bool lean,
     const float *__restrict__ depth, const ViewCalib *__restrict__ calib,
     const void *__restrict__ masks, int mask_format, const int *__restrict__ n_inst, int max_inst, int W,
-    int HW, int max_voxels, int64_t E_view, void *table, int64_t E_total, int cap_vox, VoxOut out, int cap_q,
+    int HW, int max_voxels, int64_t E_view, void *table, int64_t E_total, int cap_vox, const VoxOut &out, int cap_q,
     const uint32_t *__restrict__ q_bins, const int *__restrict__ q_rank, const int *__restrict__ n_q) {
-  const int v = blockIdx.y;
   const int no = min(n_q[v], cap_q);
-  if (blockIdx.x * 256 >= no) return;
+  if (bx * 256 >= no) return;
   const Table T = table_view(table, E_total);
   const ViewCalib c = calib[v];
   const Recip rc = make_recip(c);
   const int m = masks ? min(max(n_inst[v], 0), max_inst) : 0;
-  for (int s = blockIdx.x * 256 + threadIdx.x; s < no; s += gridDim.x * 256) {
+  for (int s = bx * 256 + threadIdx.x; s < no; s += gx * 256) {
     const int64_t e = (int64_t)v * E_view + q_bins[(size_t)v * cap_q + s];
     const int k = q_rank[(size_t)v * cap_q + s];
     if (k < max_voxels)
       emit_voxel(out, (size_t)v * cap_vox + k, c, rc, depth + (size_t)v * HW, W, T.rep[e], masks, mask_format, m,
-                 max_inst, HW, v);
+                 max_inst, HW, v, lean);
     T.kmin[e] = ~0ull;
     T.combo[e] = ~0ull;
     T.cnt[e] = 0u;
@@ -1187,11 +1274,59 @@ __global__ __launch_bounds__(256) void k_bp_fix(
     T.rep[e] = NOBIN;
   }
 }
+__global__ __launch_bounds__(256) void k_bp_fix(
+    const float *__restrict__ depth, const ViewCalib *__restrict__ calib,
+    const void *__restrict__ masks, int mask_format, const int *__restrict__ n_inst, int max_inst, int W,
+    int HW, int max_voxels, int64_t E_view, void *table, int64_t E_total, int cap_vox, VoxOut out, int cap_q,
+    const uint32_t *__restrict__ q_bins, const int *__restrict__ q_rank, const int *__restrict__ n_q) {
+  ph_fix(blockIdx.y, blockIdx.x, gridDim.x, false, depth, calib, masks, mask_format, n_inst, max_inst, W, HW, max_voxels,
+         E_view, table, E_total, cap_vox, out, cap_q, q_bins, q_rank, n_q);
+}
 
 __global__ void k_bp_finalize(int V, int max_voxels, int cap_vox, int *__restrict__ n_vox) {
   const int v = blockIdx.x * blockDim.x + threadIdx.x;
   if (v >= V) return;
   n_vox[v] = min(min(n_vox[v], cap_vox), max_voxels);
+}
+
+// ---- the chain's repair: O1..O5 and the clamp of n_vox in ONE launch, one workgroup per view -------------------
+// A repair queue belongs to one view, so the order the phases need -- lists allocated before they are gathered, gathered
+// before the selection reads them -- is an order inside the view's workgroup: a barrier (and a fence: the phases hand
+// over through global memory) between two phases.  A view with an empty queue -- every view of all but pathological
+// passes -- clamps its n_vox and leaves: what six launches did there.  A view under repair does with one workgroup what
+// the stage-by-stage kernels share among 16 or 32; the results are the same (the phases are the same functions and
+// none depends on how the work is dealt: list offsets and the order inside a list come from atomics in both forms, and
+// the selection does not depend on either).
+struct RepairArgs {
+  const float *depth;
+  const ViewCalib *calib;
+  const void *masks;
+  const int *n_inst;
+  void *table;
+  uint32_t *pix_bin, *q_list, *q_bins, *status;
+  int *q_cnt, *q_cursor, *q_rank, *n_q, *n_vox;
+  int64_t E_view, E_total;
+  int mask_format, max_inst, W, HW, key_axis, max_points, max_voxels, cap_vox, cap_q, lean;
+  VoxOut out;
+};
+static_assert(PB == 256, "k_bp_repair: every phase with 256 threads");
+__global__ __launch_bounds__(256) void k_bp_repair(dfu3d_bin_geom g, RepairArgs a) {
+  const int v = blockIdx.x;
+  if (threadIdx.x == 0) a.n_vox[v] = min(min(a.n_vox[v], a.cap_vox), a.max_voxels);     // (k_bp_finalize)
+  if (a.n_q[v] == 0) return;                          // the usual case (uniform per workgroup)
+  ph_rebin(v, 0, 1, a.depth, a.calib, g, a.W, a.HW, a.key_axis, a.n_q, a.pix_bin);
+  ph_ovf_alloc(v, 0, 1, a.table, a.E_total, a.E_view, a.cap_q, a.q_bins, a.n_q, a.q_cnt, a.q_cursor, a.HW, a.status);
+  __threadfence();
+  __syncthreads();
+  ph_ovf_gather(v, 0, 1, a.pix_bin, a.table, a.E_total, a.E_view, a.HW, a.n_q, a.q_list);
+  __threadfence();
+  __syncthreads();
+  ph_ovf_select(v, 0, 1, a.depth, a.calib, a.W, a.HW, a.key_axis, a.max_points, a.table, a.E_total, a.E_view, a.cap_q,
+                a.q_bins, a.n_q, a.q_cnt, a.q_list);
+  __threadfence();
+  __syncthreads();
+  ph_fix(v, 0, 1, a.lean != 0, a.depth, a.calib, a.masks, a.mask_format, a.n_inst, a.max_inst, a.W, a.HW, a.max_voxels,
+         a.E_view, a.table, a.E_total, a.cap_vox, a.out, a.cap_q, a.q_bins, a.q_rank, a.n_q);
 }
 
 // tier 1 (pixel_bin_fast) against the fp64 classification (pixel_bin) on n pseudo-random pixels of view 0:
@@ -1346,7 +1481,8 @@ extern "C" int dfu3d_bin_table_init(void *table, int64_t E, void *stream) {
 // Scratch carve-up.
 // blk_cnt (int32 words): n_amb[V], n_q[V], q_cursor[V], n_occ[V], bitmap[V*BW], occ[V*OW] -- everything up to here is
 //   zeroed at the start of a pass --, wpre[V*NJ], seg_list[V*NSEG], q_cnt[V*cap_q], q_bins[V*cap_q], q_rank[V*cap_q], the float32
-//   calibration constants (80 B per view), k_bp_bin's copy of the geometry records (BinCold, 208 B) and the edge tables of tier 1 (8 B x (TAB_T_MAX + TAB_P_MAX + 4) at most; the carve-up keeps round 2's 16 B)
+//   calibration constants (80 B per view), k_bp_bin's copy of the geometry records (BinCold, 208 B) and the edge tables of tier 1 (8 B x (TAB_T_MAX + TAB_P_MAX + 4) at most; the carve-up keeps round 2's 16 B),
+//   behind the tables' full room the counter of k_bp_prep_tables (4 words kept for it)
 //   (BW = 32 words per 64x16 tile, NJ = H * tiles_x, NSEG = 64-entry segments of a view's table, OW = NSEG / 4 words of
 //   occupancy bytes, cap_q: queue_cap)
 // pix_bin (uint32 words): [0, V*HW) bin id per pixel (written only for views under repair),
@@ -1371,17 +1507,18 @@ extern "C" int64_t dfu3d_backproject_scratch_words(int32_t V, int32_t H, int32_t
   if (pix_words) *pix_words = 2 * V * HW;
   const int64_t NSEG = table_segments(table_entries), OW = (NSEG + 3) / 4;
   if (blk_words) *blk_words = 4 * (int64_t)V + V * BW + V * OW + V * NJ + V * NSEG + 3 * V * cap_q + 20 * (int64_t)V + (int64_t)(sizeof(BinCold) / 4) + 16 +
-                              4 * (int64_t)(TAB_T_MAX + TAB_P_MAX) + 16;
+                              4 * (int64_t)(TAB_T_MAX + TAB_P_MAX) + 16 + 4;
   return 0;
 }
 
-extern "C" int dfu3d_backproject_bin(
+// chain != 0: the launch sequence of dfu3d_pseudo_boxes (common.hpp: dfu3d_backproject_bin_chain) -- the same kernels
+// and phases, with the tables kept across calls, the lean voxel records and the repair in one launch
+static int backproject_bin_impl(
     const float *depth, const float *calib, const void *masks, int32_t mask_format, const int32_t *n_inst,
     int32_t V, int32_t max_inst, int32_t H, int32_t W, const dfu3d_bin_geom *geom,
     int32_t key_axis, void *table, uint32_t *pix_bin, int32_t *blk_cnt, int32_t cap_vox,
     int32_t *n_vox, uint32_t *vox_pix, uint32_t *it_bits, double *it_x, double *it_y,
-    double *it_z, uint32_t *status, int32_t phases, void *stream) {
-  DFU3D_CLEAR_STALE_ERROR();
+    double *it_z, uint32_t *status, int32_t phases, void *stream, int chain) {
   if (!depth || !calib || !geom || !table || !pix_bin || !blk_cnt || !n_vox || !vox_pix ||
       !it_bits || !it_x || !it_y || !it_z || !status)
     return DFU3D_EINVAL;
@@ -1418,6 +1555,7 @@ extern "C" int dfu3d_backproject_bin(
   FastCal *fastcal = (FastCal *)(((uintptr_t)(q_rank + (size_t)V * cap_q) + 15) & ~(uintptr_t)15);   // 80 B per view
   BinCold *cold = (BinCold *)(fastcal + V);                           // written by k_bp_tables
   const float2 *tab = (const float2 *)(cold + 1);                     // edge tables of tier 1: (tJ + pJ + 4) x 8 B
+  int *tab_done = (int *)(tab + 2 * (size_t)(TAB_T_MAX + TAB_P_MAX));   // behind the room of the tables (tier 1 + tier 1.5)
   const FastGeom fg = make_fast_geom(*geom);
   int pix_bits = 1;
   while ((1ll << pix_bits) < HW64) pix_bits++;
@@ -1427,11 +1565,26 @@ extern "C" int dfu3d_backproject_bin(
   const VoxWalk Wk = {seg_list, n_occ, bitmap, wpre, NSEG, BW, NJ, tiles_x};
 
   if (phases & DFU3D_BP_BIN) {
-    if (dfu3d_fill_async(blk_cnt, 0, sizeof(int) * (4 * (size_t)V + (size_t)V * BW + (size_t)V * OW), st) != hipSuccess) return DFU3D_ELAUNCH;
-    hipLaunchKernelGGL(k_bp_prep, dim3((V + 63) / 64), dim3(64), 0, st, cal, V, H, W, fastcal);
-    DFU3D_LAUNCH_CHECK();
-    hipLaunchKernelGGL(k_bp_tables, dim3((tables_threads(fg, *geom) + 255) / 256), dim3(256), 0, st, *geom, fg, (float2 *)tab, cold);
-    DFU3D_LAUNCH_CHECK();
+    // (the chain has zeroed these words with its own counters at its head: dfu3d_bp_clear_chain)
+    if (!chain && dfu3d_fill_async(blk_cnt, 0, sizeof(int) * (4 * (size_t)V + (size_t)V * BW + (size_t)V * OW), st) != hipSuccess) return DFU3D_ELAUNCH;
+    if (chain) {
+      // the tag of the tables: the two records, byte for byte, with the padding of dfu3d_bin_geom zeroed
+      BinCold want;
+      memset(&want, 0, sizeof(want));
+      memcpy(&want.g, geom, sizeof(dfu3d_bin_geom));
+      const size_t pad0 = offsetof(dfu3d_bin_geom, max_voxels) + sizeof(int32_t), pad1 = offsetof(dfu3d_bin_geom, theta_min);
+      memset((char *)&want.g + pad0, 0, pad1 - pad0);
+      want.fg = fg;
+      const int prep_blocks = (V + PTB - 1) / PTB, tab_blocks = (tables_threads(fg, *geom) + PTB - 1) / PTB;
+      hipLaunchKernelGGL(k_bp_prep_tables, dim3(prep_blocks + tab_blocks), dim3(PTB), 0, st, cal, V, H, W, fastcal, prep_blocks,
+                         tab_blocks, want, (float2 *)tab, cold, tab_done);
+      DFU3D_LAUNCH_CHECK();
+    } else {
+      hipLaunchKernelGGL(k_bp_prep, dim3((V + 63) / 64), dim3(64), 0, st, cal, V, H, W, fastcal);
+      DFU3D_LAUNCH_CHECK();
+      hipLaunchKernelGGL(k_bp_tables, dim3((tables_threads(fg, *geom) + 255) / 256), dim3(256), 0, st, *geom, fg, (float2 *)tab, cold);
+      DFU3D_LAUNCH_CHECK();
+    }
     hipLaunchKernelGGL(k_bp_bin, dim3(tiles_x * ((tiles_y + RPT - 1) / RPT), V), dim3(PB), 0, st, depth, cal, fastcal, tab,
                        make_hot_geom(*geom, fg), W, H, tiles_x, tiles_y, key_axis, E_view, table, E_total, n_amb, q_list, pix_bits,
                        bitmap, BW, (uint8_t *)occ, OW);
@@ -1450,12 +1603,28 @@ extern "C" int dfu3d_backproject_bin(
   if (phases & DFU3D_BP_VOX) {
     // a wave per occupied segment (more of them per wave only when a view occupies more than 2 048)
     const int gx = std::min((NSEG + (VXB / 64) - 1) / (VXB / 64), VOX_GX);
-    hipLaunchKernelGGL(k_bp_vox, dim3(gx, (V + 7) / 8 * 8), dim3(VXB), 0, st, depth, cal, masks, mask_format, n_inst, max_inst, W, HW, E_view,
-                       table, E_total, cap_vox, Wk, out, key_axis, pix_bits, geom->max_points_per_voxel, geom->max_voxels,
-                       cap_q, q_bins, q_rank, n_q, status, V);
+    if (chain)
+      hipLaunchKernelGGL(k_bp_vox<true>, dim3(gx, (V + 7) / 8 * 8), dim3(VXB), 0, st, depth, cal, masks, mask_format, n_inst, max_inst, W, HW, E_view,
+                         table, E_total, cap_vox, Wk, out, key_axis, pix_bits, geom->max_points_per_voxel, geom->max_voxels,
+                         cap_q, q_bins, q_rank, n_q, status, V);
+    else
+      hipLaunchKernelGGL(k_bp_vox<false>, dim3(gx, (V + 7) / 8 * 8), dim3(VXB), 0, st, depth, cal, masks, mask_format, n_inst, max_inst, W, HW, E_view,
+                         table, E_total, cap_vox, Wk, out, key_axis, pix_bits, geom->max_points_per_voxel, geom->max_voxels,
+                         cap_q, q_bins, q_rank, n_q, status, V);
     DFU3D_LAUNCH_CHECK();
   }
-  if (phases & DFU3D_BP_REPAIR) {
+  if ((phases & DFU3D_BP_REPAIR) && chain) {
+    RepairArgs a;
+    a.depth = depth; a.calib = cal; a.masks = masks; a.n_inst = n_inst; a.table = table;
+    a.pix_bin = pix_bin; a.q_list = q_list; a.q_bins = q_bins; a.status = status;
+    a.q_cnt = q_cnt; a.q_cursor = q_cursor; a.q_rank = q_rank; a.n_q = n_q; a.n_vox = n_vox;
+    a.E_view = E_view; a.E_total = E_total;
+    a.mask_format = mask_format; a.max_inst = max_inst; a.W = W; a.HW = HW; a.key_axis = key_axis;
+    a.max_points = geom->max_points_per_voxel; a.max_voxels = geom->max_voxels; a.cap_vox = cap_vox; a.cap_q = cap_q; a.lean = 1;
+    a.out = out;
+    hipLaunchKernelGGL(k_bp_repair, dim3(V), dim3(256), 0, st, *geom, a);
+    DFU3D_LAUNCH_CHECK();
+  } else if (phases & DFU3D_BP_REPAIR) {
     // exact repair of the queued bins (more than max_points pixels, or a key collision below the cut of the
     // packed word); every kernel leaves at once for a view whose queue is empty
     const int nblk = (HW + PB - 1) / PB;
@@ -1483,5 +1652,60 @@ extern "C" int dfu3d_backproject_bin(
     hipLaunchKernelGGL(k_bp_finalize, dim3((V + 255) / 256), dim3(256), 0, st, V, geom->max_voxels, cap_vox, n_vox);
     DFU3D_LAUNCH_CHECK();
   }
+  return DFU3D_OK;
+}
+
+extern "C" int dfu3d_backproject_bin(
+    const float *depth, const float *calib, const void *masks, int32_t mask_format, const int32_t *n_inst,
+    int32_t V, int32_t max_inst, int32_t H, int32_t W, const dfu3d_bin_geom *geom,
+    int32_t key_axis, void *table, uint32_t *pix_bin, int32_t *blk_cnt, int32_t cap_vox,
+    int32_t *n_vox, uint32_t *vox_pix, uint32_t *it_bits, double *it_x, double *it_y,
+    double *it_z, uint32_t *status, int32_t phases, void *stream) {
+  DFU3D_CLEAR_STALE_ERROR();
+  return backproject_bin_impl(depth, calib, masks, mask_format, n_inst, V, max_inst, H, W, geom, key_axis, table, pix_bin,
+                              blk_cnt, cap_vox, n_vox, vox_pix, it_bits, it_x, it_y, it_z, status, phases, stream, 0);
+}
+
+int dfu3d_backproject_bin_chain(
+    const float *depth, const float *calib, const void *masks, int32_t mask_format, const int32_t *n_inst,
+    int32_t V, int32_t max_inst, int32_t H, int32_t W, const dfu3d_bin_geom *geom,
+    int32_t key_axis, void *table, uint32_t *pix_bin, int32_t *blk_cnt, int32_t cap_vox,
+    int32_t *n_vox, uint32_t *vox_pix, uint32_t *it_bits, double *it_x, double *it_y,
+    double *it_z, uint32_t *status, void *stream) {
+  return backproject_bin_impl(depth, calib, masks, mask_format, n_inst, V, max_inst, H, W, geom, key_axis, table, pix_bin,
+                              blk_cnt, cap_vox, n_vox, vox_pix, it_bits, it_x, it_y, it_z, status, DFU3D_BP_ALL, stream, 1);
+}
+
+// the words of the scratch that a pass starts from zero (counters, bit map, occupancy bytes) and up to three small regions
+// of the caller's (the chain's row counter, status word and pool cursor) in ONE launch at the head of the chain
+int dfu3d_bp_clear_chain(int32_t *blk_cnt, int32_t V, int32_t H, int32_t W, int64_t table_entries, void *a, size_t bytes_a,
+                         void *b, size_t bytes_b, void *c, size_t bytes_c, void *stream) {
+  if (!blk_cnt || V <= 0 || H <= 0 || W <= 0 || table_entries <= 0 || (((uintptr_t)blk_cnt) & 3u)) return DFU3D_EINVAL;
+  const int64_t tiles_x = (W + TILE_W - 1) / TILE_W, tiles_y = (H + TILE_H - 1) / TILE_H;
+  const int64_t BW = tiles_x * tiles_y * 32;
+  const int64_t NSEG = table_segments(table_entries), OW = (NSEG + 3) / 4;
+  const size_t n = 4 * (size_t)V + (size_t)V * BW + (size_t)V * OW, quads = (n + 3) / 4;
+  const unsigned grid = (unsigned)((quads + 255) / 256 < 8192 ? (quads + 255) / 256 : 8192);
+  hipLaunchKernelGGL(k_fill_words_and_small, dim3(grid ? grid : 1), dim3(256), 0, (hipStream_t)stream, (uint32_t *)blk_cnt, n,
+                     (uint32_t *)a, (int)(bytes_a / 4), (uint32_t *)b, (int)(bytes_b / 4), (uint32_t *)c, (int)(bytes_c / 4));
+  DFU3D_LAUNCH_CHECK();
+  return DFU3D_OK;
+}
+
+// the tag of the kept tables of a scratch (k_bp_prep_tables) made invalid: once per scratch, before its first chain call
+int dfu3d_bp_tables_forget(int32_t *blk_cnt, int32_t V, int32_t H, int32_t W, int32_t cap_vox, int32_t max_points,
+                           int64_t table_entries, void *stream) {
+  if (!blk_cnt || V <= 0 || H <= 0 || W <= 0 || cap_vox <= 0 || max_points < 1 || table_entries <= 0) return DFU3D_EINVAL;
+  const int64_t HW = (int64_t)H * W;
+  const int64_t tiles_x = (W + TILE_W - 1) / TILE_W, tiles_y = (H + TILE_H - 1) / TILE_H;
+  const int64_t BW = tiles_x * tiles_y * 32, NJ = (int64_t)H * tiles_x;
+  const int64_t cap_q = queue_cap(HW, max_points, cap_vox);
+  const int64_t NSEG = table_segments(table_entries), OW = (NSEG + 3) / 4;
+  int32_t *q_end = blk_cnt + 4 * (int64_t)V + V * BW + V * OW + V * NJ + V * NSEG + 3 * V * cap_q;
+  FastCal *fastcal = (FastCal *)(((uintptr_t)q_end + 15) & ~(uintptr_t)15);
+  BinCold *cold = (BinCold *)(fastcal + V);
+  float2 *tab = (float2 *)(cold + 1);
+  hipLaunchKernelGGL(k_bp_tables_forget, dim3(1), dim3(64), 0, (hipStream_t)stream, cold, (int *)(tab + 2 * (size_t)(TAB_T_MAX + TAB_P_MAX)));
+  DFU3D_LAUNCH_CHECK();
   return DFU3D_OK;
 }

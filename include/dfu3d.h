@@ -566,7 +566,12 @@ int dfu3d_lshape_fit(const double *px, const double *py, const double *pz,
  * radius filter (+ statistical filter), BallQuery fuse, clustering, L-shape fit,
  * box rows.  It sequences the stage entry points above on `stream`, with their
  * scratch carved from ONE caller-owned workspace (dfu3d_chain_workspace_bytes;
- * dfu3d_chain_workspace_init once, it initialises the spherical-bin table).
+ * dfu3d_chain_workspace_init once, it initialises the spherical-bin table and
+ * marks the edge tables of the bin classification "not built": the workspace
+ * keeps them across calls, with the geometry they were built from, and a call
+ * rebuilds them when its cfg->geom differs -- geom may change from call to call,
+ * the calls on one workspace being stream-ordered).  The voxel planes are
+ * workspace: a voxel under no instance mask has only its mask bits stored there.
  * Segment arrays (inst_*) are (V*max_inst); inst_r_lidar / inst_r_pseudo are the
  * radius-filter radii per instance (0 = no filter, < 0 = drop all: hazard H4).
  * plane_in: fp64 (V,4) planes to use, or NULL = seeded RANSAC keyed by view_key.
