@@ -32,6 +32,52 @@ struct ChainWs {
   int64_t table_entries;
 };
 
+// Bytes of the buffers of the path, each written ONCE, by the name it has in ChainWs: carve() slices the workspace with
+// them and dfu3d_workspace_bytes() adds up the ones a stage's entry point takes (a slice is this rounded up to 256).
+// Plain arithmetic on the sizes as given: a size function that refuses them leaves a figure <= 0, for the caller to refuse.
+struct BufBytes {
+  int64_t per_point_i32, per_point_f64;  // fov_idx, cand_idx, ag_pt, ib_pix, a_bits | a_x, a_y, a_z
+  int64_t per_view_i32, plane;           // n_fov, n_ag, K, n_vox | plane
+  int64_t per_vox_u32, per_vox_f64;      // vox_pix, b_bits | b_x, b_y, b_z
+  int64_t table, pix_bin, blk_cnt;       // dense only
+  int64_t per_slot_f64, per_slot_i32;    // px, py, pz, sx, sy, mean_d | label, sroot
+  int64_t si3, fit_ws, flags;
+  int64_t per_seg_i64, per_seg_i32;      // base_a, base_b (base_ab, rad_ab: two of them) | cnt_a, cnt_b, cnt_all, stat_enable (cnt_ab: two)
+  int64_t queue, shadow, chunk_cnt, vd_scratch, pool_cursor;
+};
+// tile_off holds, per list of tiles a kernel builds, one offset per segment and the total.  The radius filter builds one
+// list over its n segments (2S for the joint pass), the statistical filter one over S, the ball query two over S -- the
+// largest, which is what carve() takes; dfu3d_workspace_bytes answers with each stage's own figure.
+inline int64_t tile_off_bytes(int64_t segments, int lists) { return 4 * lists * (segments + 1); }
+
+BufBytes buf_bytes(const dfu3d_sizes &z) {
+  const int64_t V = z.V, S = V * z.max_inst, N = V * z.cap_n, X = V * z.cap_vox, P = z.pool_cap;
+  BufBytes b;
+  b.per_point_i32 = 4 * N; b.per_point_f64 = 8 * N;
+  b.per_view_i32 = 4 * V; b.plane = 8 * V * 4;
+  b.per_vox_u32 = 4 * X; b.per_vox_f64 = 8 * X;
+  int64_t pw = 0, bw = 0;                // (stay 0 where the size function refuses the sizes)
+  if (z.table_entries > 0)
+    dfu3d_backproject_scratch_words(z.V, z.H, z.W, z.cap_vox, z.max_points_per_voxel, z.table_entries, &pw, &bw);
+  b.table = V * z.table_entries * DFU3D_TABLE_ENTRY_BYTES; b.pix_bin = 4 * pw; b.blk_cnt = 4 * bw;
+  b.per_slot_f64 = 8 * P; b.per_slot_i32 = 4 * P; b.si3 = 4 * 3 * P; b.flags = P;
+  b.fit_ws = 8 * dfu3d_lshape_fit_ws_doubles(P, z.cap_rows);
+  b.per_seg_i64 = 8 * S; b.per_seg_i32 = 4 * S;
+  b.queue = 4 * DFU3D_RF_QUEUE_INTS(P); b.shadow = DFU3D_SHADOW_BYTES(P);
+  b.chunk_cnt = 4 * dfu3d_segments_scratch_words(z.V, z.cap_n, z.cap_vox);
+  b.vd_scratch = dfu3d_voxel_down_sample_scratch_bytes(P);
+  b.pool_cursor = 8;
+  return b;
+}
+
+dfu3d_sizes sizes_of(const dfu3d_chain_cfg *c) {
+  dfu3d_sizes z = {};
+  z.V = c->V; z.H = c->H; z.W = c->W; z.max_inst = c->max_inst; z.cap_n = c->cap_n; z.cap_vox = c->cap_vox;
+  z.cap_rows = c->cap_rows; z.max_points_per_voxel = c->geom.max_points_per_voxel; z.pool_cap = c->pool_cap;
+  z.table_entries = (int64_t)c->geom.t_n * c->geom.p_n; z.dense = c->dense; z.stat_filter = c->stat_filter;
+  return z;
+}
+
 // carve the workspace; with base == nullptr only the size is computed
 int64_t carve(const dfu3d_chain_cfg *c, char *base, ChainWs *w) {
   int64_t off = 0;
@@ -40,42 +86,37 @@ int64_t carve(const dfu3d_chain_cfg *c, char *base, ChainWs *w) {
     off += (bytes + 255) / 256 * 256;
     return p;
   };
-  const int64_t V = c->V, S = (int64_t)c->V * c->max_inst, N = V * c->cap_n, X = V * c->cap_vox, P = c->pool_cap;
+  const dfu3d_sizes z = sizes_of(c);
+  const BufBytes b = buf_bytes(z);
   ChainWs t;
-  t.fov_idx = (int32_t *)take(4 * N); t.cand_idx = (int32_t *)take(4 * N);
-  t.ag_pt = (int32_t *)take(4 * N); t.ib_pix = (int32_t *)take(4 * N);
-  t.n_fov = (int32_t *)take(4 * V); t.n_ag = (int32_t *)take(4 * V); t.K = (int32_t *)take(4 * V);
-  t.plane = (double *)take(8 * V * 4);
-  t.a_bits = (uint32_t *)take(4 * N);
-  t.a_x = (double *)take(8 * N); t.a_y = (double *)take(8 * N); t.a_z = (double *)take(8 * N);
-  t.n_vox = (int32_t *)take(4 * V);
-  t.vox_pix = (uint32_t *)take(4 * X); t.b_bits = (uint32_t *)take(4 * X);
-  t.b_x = (double *)take(8 * X); t.b_y = (double *)take(8 * X); t.b_z = (double *)take(8 * X);
-  t.table_entries = (int64_t)c->geom.t_n * c->geom.p_n;
-  int64_t pw = 0, bw = 0;
-  if (c->dense) {
-    dfu3d_backproject_scratch_words(c->V, c->H, c->W, c->cap_vox, c->geom.max_points_per_voxel, t.table_entries, &pw, &bw);
-    t.table = take(V * t.table_entries * DFU3D_TABLE_ENTRY_BYTES);
-    t.pix_bin = (uint32_t *)take(4 * pw);
-    t.blk_cnt = (int32_t *)take(4 * bw);
-  } else {
-    t.table = nullptr; t.pix_bin = nullptr; t.blk_cnt = nullptr;
-  }
-  t.px = (double *)take(8 * P); t.py = (double *)take(8 * P); t.pz = (double *)take(8 * P);
-  t.sx = (double *)take(8 * P); t.sy = (double *)take(8 * P);
-  t.label = (int32_t *)take(4 * P); t.sroot = (int32_t *)take(4 * P); t.si3 = (int32_t *)take(4 * 3 * P);
-  t.fit_ws = (double *)take(8 * dfu3d_lshape_fit_ws_doubles(P, c->cap_rows));
-  t.flags = (uint8_t *)take(P);
-  t.base_a = (int64_t *)take(8 * S); t.base_b = (int64_t *)take(8 * S); t.base_ab = (int64_t *)take(8 * 2 * S);
-  t.cnt_a = (int32_t *)take(4 * S); t.cnt_b = (int32_t *)take(4 * S); t.cnt_all = (int32_t *)take(4 * S);
-  t.cnt_ab = (int32_t *)take(4 * 2 * S); t.tile_off = (int32_t *)take(4 * (2 * S + 2));
-  t.queue = (int32_t *)take(4 * DFU3D_RF_QUEUE_INTS(P)); t.stat_enable = (int32_t *)take(4 * S);
-  t.shadow = take(DFU3D_SHADOW_BYTES(P));
-  t.chunk_cnt = (int32_t *)take(4 * dfu3d_segments_scratch_words(c->V, c->cap_n, c->cap_vox));
-  t.rad_ab = (double *)take(8 * 2 * S);
-  t.mean_d = c->stat_filter ? (double *)take(8 * P) : nullptr;
-  t.vd_scratch = c->stat_filter ? (void *)take(dfu3d_voxel_down_sample_scratch_bytes(P)) : nullptr;
-  t.pool_cursor = (int64_t *)take(8);
+  t.fov_idx = (int32_t *)take(b.per_point_i32); t.cand_idx = (int32_t *)take(b.per_point_i32);
+  t.ag_pt = (int32_t *)take(b.per_point_i32); t.ib_pix = (int32_t *)take(b.per_point_i32);
+  t.n_fov = (int32_t *)take(b.per_view_i32); t.n_ag = (int32_t *)take(b.per_view_i32); t.K = (int32_t *)take(b.per_view_i32);
+  t.plane = (double *)take(b.plane);
+  t.a_bits = (uint32_t *)take(b.per_point_i32);
+  t.a_x = (double *)take(b.per_point_f64); t.a_y = (double *)take(b.per_point_f64); t.a_z = (double *)take(b.per_point_f64);
+  t.n_vox = (int32_t *)take(b.per_view_i32);
+  t.vox_pix = (uint32_t *)take(b.per_vox_u32); t.b_bits = (uint32_t *)take(b.per_vox_u32);
+  t.b_x = (double *)take(b.per_vox_f64); t.b_y = (double *)take(b.per_vox_f64); t.b_z = (double *)take(b.per_vox_f64);
+  t.table_entries = z.table_entries;
+  t.table = c->dense ? take(b.table) : nullptr;
+  t.pix_bin = c->dense ? (uint32_t *)take(b.pix_bin) : nullptr;
+  t.blk_cnt = c->dense ? (int32_t *)take(b.blk_cnt) : nullptr;
+  t.px = (double *)take(b.per_slot_f64); t.py = (double *)take(b.per_slot_f64); t.pz = (double *)take(b.per_slot_f64);
+  t.sx = (double *)take(b.per_slot_f64); t.sy = (double *)take(b.per_slot_f64);
+  t.label = (int32_t *)take(b.per_slot_i32); t.sroot = (int32_t *)take(b.per_slot_i32); t.si3 = (int32_t *)take(b.si3);
+  t.fit_ws = (double *)take(b.fit_ws);
+  t.flags = (uint8_t *)take(b.flags);
+  t.base_a = (int64_t *)take(b.per_seg_i64); t.base_b = (int64_t *)take(b.per_seg_i64); t.base_ab = (int64_t *)take(2 * b.per_seg_i64);
+  t.cnt_a = (int32_t *)take(b.per_seg_i32); t.cnt_b = (int32_t *)take(b.per_seg_i32); t.cnt_all = (int32_t *)take(b.per_seg_i32);
+  t.cnt_ab = (int32_t *)take(2 * b.per_seg_i32); t.tile_off = (int32_t *)take(tile_off_bytes((int64_t)z.V * z.max_inst, 2));
+  t.queue = (int32_t *)take(b.queue); t.stat_enable = (int32_t *)take(b.per_seg_i32);
+  t.shadow = take(b.shadow);
+  t.chunk_cnt = (int32_t *)take(b.chunk_cnt);
+  t.rad_ab = (double *)take(2 * b.per_seg_i64);
+  t.mean_d = c->stat_filter ? (double *)take(b.per_slot_f64) : nullptr;
+  t.vd_scratch = c->stat_filter ? (void *)take(b.vd_scratch) : nullptr;
+  t.pool_cursor = (int64_t *)take(b.pool_cursor);
   if (w) *w = t;
   return off;
 }
@@ -119,37 +160,32 @@ extern "C" int64_t dfu3d_chain_workspace_bytes(const dfu3d_chain_cfg *cfg) {
 
 extern "C" int64_t dfu3d_workspace_bytes(int32_t stage, const dfu3d_sizes *z) {
   if (!z || z->V <= 0 || z->max_inst <= 0 || z->max_inst > DFU3D_MAX_INST) return DFU3D_EINVAL;
-  auto up = [](int64_t b) { return (b + 255) / 256 * 256; };
-  const int64_t V = z->V, S = V * z->max_inst, P = z->pool_cap, N = V * (int64_t)z->cap_n;
+  auto up = [](int64_t bytes) { return (bytes + 255) / 256 * 256; };
+  const int64_t S = (int64_t)z->V * z->max_inst, P = z->pool_cap;
+  const BufBytes b = buf_bytes(*z);
   switch (stage) {
     case DFU3D_STAGE_FOV_FILTER:
       return 0;
-    case DFU3D_STAGE_SEGMENTS_BUILD:                     /* chunk_cnt */
-      return (z->cap_n > 0 && z->cap_vox > 0) ? up(4 * dfu3d_segments_scratch_words(z->V, z->cap_n, z->cap_vox)) : DFU3D_EINVAL;
+    case DFU3D_STAGE_SEGMENTS_BUILD:
+      return (z->cap_n > 0 && z->cap_vox > 0) ? up(b.chunk_cnt) : DFU3D_EINVAL;
     case DFU3D_STAGE_PLANE_RANSAC:                       /* cand_idx */
-      return z->cap_n > 0 ? up(4 * N) : DFU3D_EINVAL;
+      return z->cap_n > 0 ? up(b.per_point_i32) : DFU3D_EINVAL;
     case DFU3D_STAGE_PROJECT_LABEL:                      /* ag_pt, ib_pix */
-      return z->cap_n > 0 ? 2 * up(4 * N) : DFU3D_EINVAL;
-    case DFU3D_STAGE_BACKPROJECT_BIN: {                  /* table, pix_bin, blk_cnt */
-      int64_t pw = 0, bw = 0;
-      if (z->table_entries <= 0 ||
-          dfu3d_backproject_scratch_words(z->V, z->H, z->W, z->cap_vox, z->max_points_per_voxel, z->table_entries, &pw, &bw))
-        return DFU3D_EINVAL;
-      return up(V * z->table_entries * DFU3D_TABLE_ENTRY_BYTES) + up(4 * pw) + up(4 * bw);
-    }
-    case DFU3D_STAGE_RADIUS_FILTER:                      /* shadow, tile_off, flags, queue (2S joint segments) */
-      return P > 0 ? up(DFU3D_SHADOW_BYTES(P)) + up(4 * (2 * S + 1)) + up(P) + up(4 * DFU3D_RF_QUEUE_INTS(P)) : DFU3D_EINVAL;
+      return z->cap_n > 0 ? 2 * up(b.per_point_i32) : DFU3D_EINVAL;
+    case DFU3D_STAGE_BACKPROJECT_BIN:
+      return b.blk_cnt > 0 ? up(b.table) + up(b.pix_bin) + up(b.blk_cnt) : DFU3D_EINVAL;
+    case DFU3D_STAGE_RADIUS_FILTER:                      /* (2S joint segments) */
+      return P > 0 ? up(b.shadow) + up(tile_off_bytes(2 * S, 1)) + up(b.flags) + up(b.queue) : DFU3D_EINVAL;
     case DFU3D_STAGE_STAT_FILTER:                        /* tile_off, flags, mean_d */
-      return P > 0 ? up(4 * (S + 1)) + up(P) + up(8 * P) : DFU3D_EINVAL;
-    case DFU3D_STAGE_VOXEL_DOWN_SAMPLE:                  /* scratch */
-      return P > 0 ? up(dfu3d_voxel_down_sample_scratch_bytes(P)) : DFU3D_EINVAL;
-    case DFU3D_STAGE_BALLQUERY_FUSE:                     /* tile_off, flags */
-      return P > 0 ? up(4 * (2 * S + 2)) + up(P) : DFU3D_EINVAL;
+      return P > 0 ? up(tile_off_bytes(S, 1)) + up(b.flags) + up(b.per_slot_f64) : DFU3D_EINVAL;
+    case DFU3D_STAGE_VOXEL_DOWN_SAMPLE:
+      return P > 0 ? up(b.vd_scratch) : DFU3D_EINVAL;
+    case DFU3D_STAGE_BALLQUERY_FUSE:
+      return P > 0 ? up(tile_off_bytes(S, 2)) + up(b.flags) : DFU3D_EINVAL;
     case DFU3D_STAGE_RANGE_CLUSTER:                      /* sx, sy, si */
-      return P > 0 ? 2 * up(8 * P) + up(12 * P) : DFU3D_EINVAL;
+      return P > 0 ? 2 * up(b.per_slot_f64) + up(b.si3) : DFU3D_EINVAL;
     case DFU3D_STAGE_LSHAPE_FIT:                         /* sx, sy, sroot, fit_ws */
-      return (P > 0 && z->cap_rows > 0)
-                 ? 2 * up(8 * P) + up(4 * P) + up(8 * dfu3d_lshape_fit_ws_doubles(P, z->cap_rows)) : DFU3D_EINVAL;
+      return (P > 0 && z->cap_rows > 0) ? 2 * up(b.per_slot_f64) + up(b.per_slot_i32) + up(b.fit_ws) : DFU3D_EINVAL;
     case DFU3D_STAGE_PSEUDO_BOXES: {
       dfu3d_chain_cfg c = {};
       c.V = z->V; c.H = z->H; c.W = z->W; c.max_inst = z->max_inst; c.cap_n = z->cap_n; c.cap_vox = z->cap_vox;

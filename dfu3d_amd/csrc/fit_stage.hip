@@ -1716,7 +1716,9 @@ extern "C" int dfu3d_range_cluster(const double *px, const double *py, const int
 extern "C" int64_t dfu3d_lshape_fit_ws_doubles(int64_t pool_cap, int32_t cap_rows) {
   if (pool_cap <= 0 || cap_rows <= 0) return DFU3D_EINVAL;
   const int64_t cap_big = pool_cap / LDS_MEMBERS + 1;
-  return 2 + (int64_t)8 * fit_cap_q(cap_rows) + (cap_big / 2 + 1) + cap_big * MAXTH;
+  if (cap_big > 0x7FFFFFFF) return DFU3D_ERANGE;       // (dfu3d_lshape_fit takes cap_big as an int: pools of 2^42 points)
+  static double origin[1];                             // fit_ws_view on a base nobody dereferences: the end of big_cost is the size
+  return (fit_ws_view(origin, cap_rows, (int)cap_big).big_cost - origin) + cap_big * MAXTH;
 }
 
 extern "C" int dfu3d_lshape_fit(const double *px, const double *py, const double *pz,

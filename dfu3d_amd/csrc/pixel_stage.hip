@@ -1478,15 +1478,6 @@ extern "C" int dfu3d_bin_table_init(void *table, int64_t E, void *stream) {
   return DFU3D_OK;
 }
 
-// Scratch carve-up.
-// blk_cnt (int32 words): n_amb[V], n_q[V], q_cursor[V], n_occ[V], bitmap[V*BW], occ[V*OW] -- everything up to here is
-//   zeroed at the start of a pass --, wpre[V*NJ], seg_list[V*NSEG], q_cnt[V*cap_q], q_bins[V*cap_q], q_rank[V*cap_q], the float32
-//   calibration constants (80 B per view), k_bp_bin's copy of the geometry records (BinCold, 208 B) and the edge tables of tier 1 (8 B x (TAB_T_MAX + TAB_P_MAX + 4) at most; the carve-up keeps round 2's 16 B),
-//   behind the tables' full room the counter of k_bp_prep_tables (4 words kept for it)
-//   (BW = 32 words per 64x16 tile, NJ = H * tiles_x, NSEG = 64-entry segments of a view's table, OW = NSEG / 4 words of
-//   occupancy bytes, cap_q: queue_cap)
-// pix_bin (uint32 words): [0, V*HW) bin id per pixel (written only for views under repair),
-//   [V*HW, 2*V*HW) undecided-pixel lists, later the pixel lists of the repair.
 static inline int queue_cap(int64_t HW, int max_points, int cap_vox) {
   if (DBG_COMBO_KEYBITS < 64) return cap_vox;             // test builds provoke the repair for a large share of the bins
   const int64_t q = HW / (max_points + 1) + 1 + 4096;     // bins over the cap + room for key collisions
@@ -1496,18 +1487,68 @@ static inline int queue_cap(int64_t HW, int max_points, int cap_vox) {
 // segments (64 entries) and occupancy words of a view's table; an upper bound when the geometry is not known yet
 static inline int64_t table_segments(int64_t E_view) { return (E_view + 63) >> SEG_SHIFT; }
 
+// The back-projection scratch blk_cnt (int32 words), in the order of the members.  bp_scratch() is its ONLY definition:
+// the size function, both launch sequences, the chain's clear and the reset of the tables' tag take it from there.
+// (pix_bin, uint32 words, needs no carving: [0, V*HW) bin id per pixel, written only for views under repair;
+// [V*HW, 2*V*HW) undecided-pixel lists, later the pixel lists of the repair.)
+struct BpScratch {
+  int *n_amb, *n_q, *q_cursor, *n_occ;   // [V] each
+  uint32_t *bitmap;                      // [V*BW], BW = 32 words per 64x16 tile
+  uint32_t *occ;                         // [V*OW] occupancy bytes of a view's table, OW = NSEG / 4 words
+  int64_t zero_words;                    // everything up to here is zeroed at the start of a pass
+  uint32_t *wpre;                        // [V*NJ], NJ = H * tiles_x
+  int *seg_list;                         // [V*NSEG], NSEG = 64-entry segments of a view's table
+  int *q_cnt;                            // [V*cap_q], cap_q: queue_cap
+  uint32_t *q_bins;                      // [V*cap_q]
+  int *q_rank;                           // [V*cap_q]
+  FastCal *fastcal;                      // [V] float32 calibration constants (80 B per view), 16-byte aligned
+  BinCold *cold;                         // k_bp_bin's copy of the geometry records (208 B) = the tag of the kept tables
+  float2 *tab;                           // edge tables: tier 1 (8 B x (tJ + pJ + 4)), tier 1.5 behind it where make_fast_geom finds room
+  int *tab_done;                         // behind the tables' full room: the counter of k_bp_prep_tables
+  int64_t words;                         // the whole scratch: what the caller allocates
+  int tiles_x, tiles_y, BW, NJ, NSEG, OW, cap_q;   // (as the kernels take them: in range under the entry points' checks)
+};
+constexpr int64_t BP_FASTCAL_ALIGN_WORDS = 4;      // room for the shift that aligns FastCal (at most 3 words)
+constexpr int64_t BP_TAB_WORDS = 4 * (int64_t)(TAB_T_MAX + TAB_P_MAX);   // 2 x (TAB_T_MAX + TAB_P_MAX) cells of 8 B: what mid_ok counts on
+constexpr int64_t BP_TAB_DONE_WORDS = 4;           // one counter; four words kept for it
+constexpr int64_t BP_PAD_WORDS = 28;               // historical padding behind everything (round 2's carve-up), kept so that sizes do not move
+
+// blk_cnt == nullptr: the counts and `words` only (the pointers stay null).  The callers validate the sizes.
+static BpScratch bp_scratch(int32_t *blk_cnt, int64_t V, int64_t H, int64_t W, int cap_vox, int max_points, int64_t E_view) {
+  const int64_t tiles_x = (W + TILE_W - 1) / TILE_W, tiles_y = (H + TILE_H - 1) / TILE_H;
+  const int64_t BW = tiles_x * tiles_y * 32, NJ = H * tiles_x;
+  const int64_t NSEG = table_segments(E_view), OW = (NSEG + 3) / 4;
+  const int64_t cap_q = queue_cap(H * W, max_points, cap_vox);
+  int64_t off = 0;
+  auto take = [&](int64_t words) { int32_t *p = blk_cnt ? blk_cnt + off : nullptr; off += words; return p; };
+  BpScratch S;
+  S.n_amb = take(V); S.n_q = take(V); S.q_cursor = take(V); S.n_occ = take(V);
+  S.bitmap = (uint32_t *)take(V * BW);
+  S.occ = (uint32_t *)take(V * OW);
+  S.zero_words = off;
+  S.wpre = (uint32_t *)take(V * NJ);
+  S.seg_list = take(V * NSEG);
+  S.q_cnt = take(V * cap_q);
+  S.q_bins = (uint32_t *)take(V * cap_q);
+  S.q_rank = take(V * cap_q);
+  const int64_t shift = blk_cnt ? (int64_t)((0 - (uintptr_t)(blk_cnt + off)) & 15u) / 4 : 0;
+  take(shift);
+  S.fastcal = (FastCal *)take(V * (int64_t)(sizeof(FastCal) / 4));
+  S.cold = (BinCold *)take(sizeof(BinCold) / 4);
+  S.tab = (float2 *)take(BP_TAB_WORDS);
+  S.tab_done = take(BP_TAB_DONE_WORDS);
+  S.words = off - shift + BP_FASTCAL_ALIGN_WORDS + BP_PAD_WORDS;
+  S.tiles_x = (int)tiles_x; S.tiles_y = (int)tiles_y; S.BW = (int)BW; S.NJ = (int)NJ;
+  S.NSEG = (int)NSEG; S.OW = (int)OW; S.cap_q = (int)cap_q;
+  return S;
+}
+
 extern "C" int64_t dfu3d_backproject_scratch_words(int32_t V, int32_t H, int32_t W,
                                                     int32_t cap_vox, int32_t max_points, int64_t table_entries,
                                                     int64_t *pix_words, int64_t *blk_words) {
   if (V <= 0 || H <= 0 || W <= 0 || cap_vox <= 0 || max_points < 1 || table_entries <= 0) return DFU3D_EINVAL;
-  const int64_t HW = (int64_t)H * W;
-  const int64_t tiles_x = (W + TILE_W - 1) / TILE_W, tiles_y = (H + TILE_H - 1) / TILE_H;
-  const int64_t BW = tiles_x * tiles_y * 32, NJ = (int64_t)H * tiles_x;
-  const int64_t cap_q = queue_cap(HW, max_points, cap_vox);
-  if (pix_words) *pix_words = 2 * V * HW;
-  const int64_t NSEG = table_segments(table_entries), OW = (NSEG + 3) / 4;
-  if (blk_words) *blk_words = 4 * (int64_t)V + V * BW + V * OW + V * NJ + V * NSEG + 3 * V * cap_q + 20 * (int64_t)V + (int64_t)(sizeof(BinCold) / 4) + 16 +
-                              4 * (int64_t)(TAB_T_MAX + TAB_P_MAX) + 16 + 4;
+  if (pix_words) *pix_words = 2 * (int64_t)V * H * W;
+  if (blk_words) *blk_words = bp_scratch(nullptr, V, H, W, cap_vox, max_points, table_entries).words;
   return 0;
 }
 
@@ -1533,40 +1574,22 @@ static int backproject_bin_impl(
   if (geom->max_points_per_voxel < 1) return DFU3D_EINVAL;
   if (((uintptr_t)blk_cnt & 7u) != 0) return DFU3D_EINVAL;   // 64-bit counters in front
   const int HW = (int)HW64;
-  const int tiles_x = (W + TILE_W - 1) / TILE_W, tiles_y = (H + TILE_H - 1) / TILE_H;
-  const int BW = tiles_x * tiles_y * 32, NJ = H * tiles_x;
-  const int cap_q = queue_cap(HW64, geom->max_points_per_voxel, cap_vox);
   const int64_t E_view = (int64_t)geom->t_n * geom->p_n;
   if (E_view >= (1ll << 29)) return DFU3D_ERANGE;    // k_bp_bin addresses a view's 8-byte planes with 32-bit byte offsets
   const int64_t E_total = E_view * V;
   hipStream_t st = (hipStream_t)stream;
-  const int NSEG = (int)table_segments(E_view), OW = (NSEG + 3) / 4;       // OW: words of the occupancy bytes
-  int *n_amb = blk_cnt;
-  int *n_q = n_amb + V;
-  int *q_cursor = n_q + V;
-  int *n_occ = q_cursor + V;
-  uint32_t *bitmap = (uint32_t *)(n_occ + V);
-  uint32_t *occ = bitmap + (size_t)V * BW;
-  uint32_t *wpre = occ + (size_t)V * OW;
-  int *seg_list = (int *)(wpre + (size_t)V * NJ);
-  int *q_cnt = seg_list + (size_t)V * NSEG;
-  uint32_t *q_bins = (uint32_t *)(q_cnt + (size_t)V * cap_q);
-  int *q_rank = (int *)(q_bins + (size_t)V * cap_q);
-  FastCal *fastcal = (FastCal *)(((uintptr_t)(q_rank + (size_t)V * cap_q) + 15) & ~(uintptr_t)15);   // 80 B per view
-  BinCold *cold = (BinCold *)(fastcal + V);                           // written by k_bp_tables
-  const float2 *tab = (const float2 *)(cold + 1);                     // edge tables of tier 1: (tJ + pJ + 4) x 8 B
-  int *tab_done = (int *)(tab + 2 * (size_t)(TAB_T_MAX + TAB_P_MAX));   // behind the room of the tables (tier 1 + tier 1.5)
+  const BpScratch S = bp_scratch(blk_cnt, V, H, W, cap_vox, geom->max_points_per_voxel, E_view);
   const FastGeom fg = make_fast_geom(*geom);
   int pix_bits = 1;
   while ((1ll << pix_bits) < HW64) pix_bits++;
   uint32_t *q_list = pix_bin + (size_t)V * HW;       // undecided pixels first, repair lists later
   const ViewCalib *cal = (const ViewCalib *)calib;
   const VoxOut out = {vox_pix, it_bits, it_x, it_y, it_z};
-  const VoxWalk Wk = {seg_list, n_occ, bitmap, wpre, NSEG, BW, NJ, tiles_x};
+  const VoxWalk Wk = {S.seg_list, S.n_occ, S.bitmap, S.wpre, S.NSEG, S.BW, S.NJ, S.tiles_x};
 
   if (phases & DFU3D_BP_BIN) {
     // (the chain has zeroed these words with its own counters at its head: dfu3d_bp_clear_chain)
-    if (!chain && dfu3d_fill_async(blk_cnt, 0, sizeof(int) * (4 * (size_t)V + (size_t)V * BW + (size_t)V * OW), st) != hipSuccess) return DFU3D_ELAUNCH;
+    if (!chain && dfu3d_fill_async(blk_cnt, 0, sizeof(int) * (size_t)S.zero_words, st) != hipSuccess) return DFU3D_ELAUNCH;
     if (chain) {
       // the tag of the tables: the two records, byte for byte, with the padding of dfu3d_bin_geom zeroed
       BinCold want;
@@ -1576,51 +1599,51 @@ static int backproject_bin_impl(
       memset((char *)&want.g + pad0, 0, pad1 - pad0);
       want.fg = fg;
       const int prep_blocks = (V + PTB - 1) / PTB, tab_blocks = (tables_threads(fg, *geom) + PTB - 1) / PTB;
-      hipLaunchKernelGGL(k_bp_prep_tables, dim3(prep_blocks + tab_blocks), dim3(PTB), 0, st, cal, V, H, W, fastcal, prep_blocks,
-                         tab_blocks, want, (float2 *)tab, cold, tab_done);
+      hipLaunchKernelGGL(k_bp_prep_tables, dim3(prep_blocks + tab_blocks), dim3(PTB), 0, st, cal, V, H, W, S.fastcal, prep_blocks,
+                         tab_blocks, want, S.tab, S.cold, S.tab_done);
       DFU3D_LAUNCH_CHECK();
     } else {
-      hipLaunchKernelGGL(k_bp_prep, dim3((V + 63) / 64), dim3(64), 0, st, cal, V, H, W, fastcal);
+      hipLaunchKernelGGL(k_bp_prep, dim3((V + 63) / 64), dim3(64), 0, st, cal, V, H, W, S.fastcal);
       DFU3D_LAUNCH_CHECK();
-      hipLaunchKernelGGL(k_bp_tables, dim3((tables_threads(fg, *geom) + 255) / 256), dim3(256), 0, st, *geom, fg, (float2 *)tab, cold);
+      hipLaunchKernelGGL(k_bp_tables, dim3((tables_threads(fg, *geom) + 255) / 256), dim3(256), 0, st, *geom, fg, S.tab, S.cold);
       DFU3D_LAUNCH_CHECK();
     }
-    hipLaunchKernelGGL(k_bp_bin, dim3(tiles_x * ((tiles_y + RPT - 1) / RPT), V), dim3(PB), 0, st, depth, cal, fastcal, tab,
-                       make_hot_geom(*geom, fg), W, H, tiles_x, tiles_y, key_axis, E_view, table, E_total, n_amb, q_list, pix_bits,
-                       bitmap, BW, (uint8_t *)occ, OW);
+    hipLaunchKernelGGL(k_bp_bin, dim3(S.tiles_x * ((S.tiles_y + RPT - 1) / RPT), V), dim3(PB), 0, st, depth, cal, S.fastcal, S.tab,
+                       make_hot_geom(*geom, fg), W, H, S.tiles_x, S.tiles_y, key_axis, E_view, table, E_total, S.n_amb, q_list, pix_bits,
+                       S.bitmap, S.BW, (uint8_t *)S.occ, S.OW);
     DFU3D_LAUNCH_CHECK();
   }
   if (phases & DFU3D_BP_AMB) {
     hipLaunchKernelGGL(k_bp_bin_amb, dim3(64, V), dim3(256), 0, st, depth, cal, *geom, W, HW,
-                       key_axis, E_view, table, E_total, n_amb, q_list, status, pix_bits, bitmap, BW, tiles_x, (uint8_t *)occ, OW);
+                       key_axis, E_view, table, E_total, S.n_amb, q_list, status, pix_bits, S.bitmap, S.BW, S.tiles_x, (uint8_t *)S.occ, S.OW);
     DFU3D_LAUNCH_CHECK();
   }
   if (phases & DFU3D_BP_MARK) {
-    hipLaunchKernelGGL(k_bp_scan, dim3(V), dim3(SCB), 0, st, BW, NJ, tiles_x, bitmap, wpre, n_vox, cap_vox, status, occ, OW,
-                       NSEG, seg_list, n_occ);
+    hipLaunchKernelGGL(k_bp_scan, dim3(V), dim3(SCB), 0, st, S.BW, S.NJ, S.tiles_x, S.bitmap, S.wpre, n_vox, cap_vox, status, S.occ, S.OW,
+                       S.NSEG, S.seg_list, S.n_occ);
     DFU3D_LAUNCH_CHECK();
   }
   if (phases & DFU3D_BP_VOX) {
     // a wave per occupied segment (more of them per wave only when a view occupies more than 2 048)
-    const int gx = std::min((NSEG + (VXB / 64) - 1) / (VXB / 64), VOX_GX);
+    const int gx = std::min((S.NSEG + (VXB / 64) - 1) / (VXB / 64), VOX_GX);
     if (chain)
       hipLaunchKernelGGL(k_bp_vox<true>, dim3(gx, (V + 7) / 8 * 8), dim3(VXB), 0, st, depth, cal, masks, mask_format, n_inst, max_inst, W, HW, E_view,
                          table, E_total, cap_vox, Wk, out, key_axis, pix_bits, geom->max_points_per_voxel, geom->max_voxels,
-                         cap_q, q_bins, q_rank, n_q, status, V);
+                         S.cap_q, S.q_bins, S.q_rank, S.n_q, status, V);
     else
       hipLaunchKernelGGL(k_bp_vox<false>, dim3(gx, (V + 7) / 8 * 8), dim3(VXB), 0, st, depth, cal, masks, mask_format, n_inst, max_inst, W, HW, E_view,
                          table, E_total, cap_vox, Wk, out, key_axis, pix_bits, geom->max_points_per_voxel, geom->max_voxels,
-                         cap_q, q_bins, q_rank, n_q, status, V);
+                         S.cap_q, S.q_bins, S.q_rank, S.n_q, status, V);
     DFU3D_LAUNCH_CHECK();
   }
   if ((phases & DFU3D_BP_REPAIR) && chain) {
     RepairArgs a;
     a.depth = depth; a.calib = cal; a.masks = masks; a.n_inst = n_inst; a.table = table;
-    a.pix_bin = pix_bin; a.q_list = q_list; a.q_bins = q_bins; a.status = status;
-    a.q_cnt = q_cnt; a.q_cursor = q_cursor; a.q_rank = q_rank; a.n_q = n_q; a.n_vox = n_vox;
+    a.pix_bin = pix_bin; a.q_list = q_list; a.q_bins = S.q_bins; a.status = status;
+    a.q_cnt = S.q_cnt; a.q_cursor = S.q_cursor; a.q_rank = S.q_rank; a.n_q = S.n_q; a.n_vox = n_vox;
     a.E_view = E_view; a.E_total = E_total;
     a.mask_format = mask_format; a.max_inst = max_inst; a.W = W; a.HW = HW; a.key_axis = key_axis;
-    a.max_points = geom->max_points_per_voxel; a.max_voxels = geom->max_voxels; a.cap_vox = cap_vox; a.cap_q = cap_q; a.lean = 1;
+    a.max_points = geom->max_points_per_voxel; a.max_voxels = geom->max_voxels; a.cap_vox = cap_vox; a.cap_q = S.cap_q; a.lean = 1;
     a.out = out;
     hipLaunchKernelGGL(k_bp_repair, dim3(V), dim3(256), 0, st, *geom, a);
     DFU3D_LAUNCH_CHECK();
@@ -1631,23 +1654,23 @@ static int backproject_bin_impl(
     // (grids of a few workgroups per view: the queues are empty in all but pathological passes, and 75 000 workgroups that
     // start only to find that out cost 25 us per pass; a view under repair walks its pixels with the grid's stride)
     hipLaunchKernelGGL(k_bp_rebin, dim3(nblk < 16 ? nblk : 16, V), dim3(PB), 0, st, depth, cal, *geom, W, HW,
-                       key_axis, n_q, pix_bin);
+                       key_axis, S.n_q, pix_bin);
     DFU3D_LAUNCH_CHECK();
-    const int ga = (cap_q + 255) / 256;
-    hipLaunchKernelGGL(k_ovf_alloc, dim3(ga < 16 ? ga : 16, V), dim3(256), 0, st, table, E_total, E_view, cap_q,
-                       q_bins, n_q, q_cnt, q_cursor, HW, status);
+    const int ga = (S.cap_q + 255) / 256;
+    hipLaunchKernelGGL(k_ovf_alloc, dim3(ga < 16 ? ga : 16, V), dim3(256), 0, st, table, E_total, E_view, S.cap_q,
+                       S.q_bins, S.n_q, S.q_cnt, S.q_cursor, HW, status);
     DFU3D_LAUNCH_CHECK();
     const int nblk4 = (HW + PBLK - 1) / PBLK;
     hipLaunchKernelGGL(k_ovf_gather, dim3(nblk4 < 16 ? nblk4 : 16, V), dim3(PB), 0, st, pix_bin, table, E_total,
-                       E_view, HW, n_q, q_list);
+                       E_view, HW, S.n_q, q_list);
     DFU3D_LAUNCH_CHECK();
-    hipLaunchKernelGGL(k_ovf_select, dim3(cap_q < 32 ? cap_q : 32, V), dim3(256), 0, st, depth, cal, W, HW,
-                       key_axis, geom->max_points_per_voxel, table, E_total, E_view, cap_q,
-                       q_bins, n_q, q_cnt, q_list);
+    hipLaunchKernelGGL(k_ovf_select, dim3(S.cap_q < 32 ? S.cap_q : 32, V), dim3(256), 0, st, depth, cal, W, HW,
+                       key_axis, geom->max_points_per_voxel, table, E_total, E_view, S.cap_q,
+                       S.q_bins, S.n_q, S.q_cnt, q_list);
     DFU3D_LAUNCH_CHECK();
     hipLaunchKernelGGL(k_bp_fix, dim3(ga < 16 ? ga : 16, V), dim3(256), 0, st, depth, cal, masks, mask_format, n_inst,
-                       max_inst, W, HW, geom->max_voxels, E_view, table, E_total, cap_vox, out, cap_q, q_bins, q_rank,
-                       n_q);
+                       max_inst, W, HW, geom->max_voxels, E_view, table, E_total, cap_vox, out, S.cap_q, S.q_bins, S.q_rank,
+                       S.n_q);
     DFU3D_LAUNCH_CHECK();
     hipLaunchKernelGGL(k_bp_finalize, dim3((V + 255) / 256), dim3(256), 0, st, V, geom->max_voxels, cap_vox, n_vox);
     DFU3D_LAUNCH_CHECK();
@@ -1681,10 +1704,8 @@ int dfu3d_backproject_bin_chain(
 int dfu3d_bp_clear_chain(int32_t *blk_cnt, int32_t V, int32_t H, int32_t W, int64_t table_entries, void *a, size_t bytes_a,
                          void *b, size_t bytes_b, void *c, size_t bytes_c, void *stream) {
   if (!blk_cnt || V <= 0 || H <= 0 || W <= 0 || table_entries <= 0 || (((uintptr_t)blk_cnt) & 3u)) return DFU3D_EINVAL;
-  const int64_t tiles_x = (W + TILE_W - 1) / TILE_W, tiles_y = (H + TILE_H - 1) / TILE_H;
-  const int64_t BW = tiles_x * tiles_y * 32;
-  const int64_t NSEG = table_segments(table_entries), OW = (NSEG + 3) / 4;
-  const size_t n = 4 * (size_t)V + (size_t)V * BW + (size_t)V * OW, quads = (n + 3) / 4;
+  // (cap_vox, max_points: only the queues behind the zeroed words depend on them)
+  const size_t n = (size_t)bp_scratch(nullptr, V, H, W, 1, 1, table_entries).zero_words, quads = (n + 3) / 4;
   const unsigned grid = (unsigned)((quads + 255) / 256 < 8192 ? (quads + 255) / 256 : 8192);
   hipLaunchKernelGGL(k_fill_words_and_small, dim3(grid ? grid : 1), dim3(256), 0, (hipStream_t)stream, (uint32_t *)blk_cnt, n,
                      (uint32_t *)a, (int)(bytes_a / 4), (uint32_t *)b, (int)(bytes_b / 4), (uint32_t *)c, (int)(bytes_c / 4));
@@ -1696,16 +1717,8 @@ int dfu3d_bp_clear_chain(int32_t *blk_cnt, int32_t V, int32_t H, int32_t W, int6
 int dfu3d_bp_tables_forget(int32_t *blk_cnt, int32_t V, int32_t H, int32_t W, int32_t cap_vox, int32_t max_points,
                            int64_t table_entries, void *stream) {
   if (!blk_cnt || V <= 0 || H <= 0 || W <= 0 || cap_vox <= 0 || max_points < 1 || table_entries <= 0) return DFU3D_EINVAL;
-  const int64_t HW = (int64_t)H * W;
-  const int64_t tiles_x = (W + TILE_W - 1) / TILE_W, tiles_y = (H + TILE_H - 1) / TILE_H;
-  const int64_t BW = tiles_x * tiles_y * 32, NJ = (int64_t)H * tiles_x;
-  const int64_t cap_q = queue_cap(HW, max_points, cap_vox);
-  const int64_t NSEG = table_segments(table_entries), OW = (NSEG + 3) / 4;
-  int32_t *q_end = blk_cnt + 4 * (int64_t)V + V * BW + V * OW + V * NJ + V * NSEG + 3 * V * cap_q;
-  FastCal *fastcal = (FastCal *)(((uintptr_t)q_end + 15) & ~(uintptr_t)15);
-  BinCold *cold = (BinCold *)(fastcal + V);
-  float2 *tab = (float2 *)(cold + 1);
-  hipLaunchKernelGGL(k_bp_tables_forget, dim3(1), dim3(64), 0, (hipStream_t)stream, cold, (int *)(tab + 2 * (size_t)(TAB_T_MAX + TAB_P_MAX)));
+  const BpScratch S = bp_scratch(blk_cnt, V, H, W, cap_vox, max_points, table_entries);
+  hipLaunchKernelGGL(k_bp_tables_forget, dim3(1), dim3(64), 0, (hipStream_t)stream, S.cold, S.tab_done);
   DFU3D_LAUNCH_CHECK();
   return DFU3D_OK;
 }

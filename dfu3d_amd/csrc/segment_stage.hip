@@ -340,6 +340,11 @@ constexpr int RF_LQ_CAP = 1 << 16;         // "long" queries: more candidate ran
 constexpr int RF_ITEM_CAP = 1 << 20;       // their (query, range) work items
 constexpr int RF_INLINE_CAND = 2;
 constexpr int RF_WORK_HDR = 32;            // ints: [0] long queries, [16] work items
+// RfScratch::work, in ints: RF_WORK_HDR counters | ucount, one per segment id | long-query records (4 ints) | work items (2 ints)
+constexpr int RF_UCOUNT = 1 << 16;         // segment ids are below RF_NOSEG
+constexpr int RF_WORK_LQ = RF_WORK_HDR + RF_UCOUNT;
+constexpr int RF_WORK_ITEMS = RF_WORK_LQ + 4 * RF_LQ_CAP;
+constexpr int RF_WORK_INTS = RF_WORK_ITEMS + 2 * RF_ITEM_CAP;
 constexpr uint32_t RF_INCOH = 0x80000000u; // upos: position | RF_INCOH
 
 // bound on |float32 distance - true distance| for a query at (x,y,z) and neighbours within ~r of it:
@@ -424,7 +429,7 @@ struct RfScratch {
   float4 *uent;             // (x, y, z, shadow word) of listed point k of range rg at rg * RF_WLIST + k, k < #listed (rrec[.][3])
   uint32_t *upos;           // its pool position | RF_INCOH
   float4 *ulist;            // (x, y, z, position) of incoherent points that found their range's slots full: per segment, at seg_base[s] + k, k < ucount[s]
-  int *work;                // RF_WORK_HDR counters | ucount (65536) | long-query records (4 ints) | work items (2 ints)
+  int *work;                // RF_WORK_INTS: counters, ucount, long-query records at RF_WORK_LQ, work items at RF_WORK_ITEMS
   int *ucount;
   const long long *seg_base;
 };
@@ -432,6 +437,43 @@ __host__ __device__ inline long long rf_queue_part_cap(long long pool_cap) {
   const long long nwg = (pool_cap + RF_WG - 1) / RF_WG;
   return ((nwg + RF_QSHARDS - 1) / RF_QSHARDS) * RF_WG;
 }
+
+// The cut of the caller's `shadow` buffer, its ONLY definition: the shadow proper (16 B per pool slot), then per RANGE of
+// 512 slots (one more than the pool holds) a record of two boxes and a count and the range's U slots, the per-segment
+// overflow lists (16 B per slot, at the segments' own pool positions), then `work`.  shadow == nullptr: `bytes` only.
+struct RfCut {
+  float4 *pq;
+  RfScratch W;              // (flags, queue, seg_base: the caller's)
+  int64_t n_ranges, bytes;
+};
+inline RfCut rf_cut(void *shadow, int64_t pool_cap) {
+  int64_t off = 0;
+  auto take = [&](int64_t bytes) { char *p = shadow ? (char *)shadow + off : nullptr; off += bytes; return p; };
+  RfCut C = {};
+  C.n_ranges = ((pool_cap + (1 << BOX_SHIFT) - 1) >> BOX_SHIFT) + 1;
+  C.pq = (float4 *)take(sizeof(float4) * pool_cap);
+  C.W.rrec = (float *)take(sizeof(float) * BOX_FLOATS * C.n_ranges);
+  C.W.uent = (float4 *)take(sizeof(float4) * RF_WLIST * C.n_ranges);
+  C.W.upos = (uint32_t *)take(sizeof(uint32_t) * RF_WLIST * C.n_ranges);
+  C.W.ulist = (float4 *)take(sizeof(float4) * pool_cap);
+  C.W.work = (int *)take(sizeof(int) * RF_WORK_INTS);
+  C.W.ucount = C.W.work ? C.W.work + RF_WORK_HDR : nullptr;
+  C.W.qcap = rf_queue_part_cap(pool_cap);
+  C.bytes = off;
+  return C;
+}
+// The public size macros are ABI and spell the same numbers as literals: per slot, per range, constant; header and parts of the queue
+constexpr int64_t RF_RANGE_BYTES = 4 * BOX_FLOATS + (16 + 4) * RF_WLIST;
+static_assert(DFU3D_SHADOW_BYTES(2) - DFU3D_SHADOW_BYTES(1) == 2 * sizeof(float4), "DFU3D_SHADOW_BYTES: bytes per pool slot");
+static_assert(DFU3D_SHADOW_BYTES(1 << BOX_SHIFT) - DFU3D_SHADOW_BYTES((1 << BOX_SHIFT) - 1) == 2 * sizeof(float4) &&
+              DFU3D_SHADOW_BYTES((1 << BOX_SHIFT) + 1) - DFU3D_SHADOW_BYTES(1 << BOX_SHIFT) == 2 * sizeof(float4) + RF_RANGE_BYTES,
+              "DFU3D_SHADOW_BYTES: slots of a range (BOX_SHIFT), bytes per range (BOX_FLOATS, RF_WLIST)");
+static_assert(DFU3D_SHADOW_BYTES(0) == RF_RANGE_BYTES + 4 * (int64_t)RF_WORK_INTS,
+              "DFU3D_SHADOW_BYTES: constant term (RF_WORK_HDR, RF_UCOUNT, RF_LQ_CAP, RF_ITEM_CAP)");
+static_assert(DFU3D_RF_QUEUE_INTS(0) == RF_QHDR && DFU3D_RF_QUEUE_INTS(1) == RF_QHDR + (int64_t)RF_QSHARDS * RF_WG &&
+              DFU3D_RF_QUEUE_INTS((int64_t)RF_QSHARDS * RF_WG) == DFU3D_RF_QUEUE_INTS(1) &&
+              DFU3D_RF_QUEUE_INTS((int64_t)RF_QSHARDS * RF_WG + 1) == RF_QHDR + 2 * (int64_t)RF_QSHARDS * RF_WG,
+              "DFU3D_RF_QUEUE_INTS: RF_QHDR + RF_QSHARDS parts of rf_queue_part_cap (RF_WG)");
 // append to the part of the queue that belongs to `key` (any number; consecutive keys use different counters)
 __device__ __forceinline__ void rf_queue_push(const RfScratch &W, long long key, unsigned long long mask, bool mine, uint32_t gpos) {
   const int lane = lane_id();
@@ -799,7 +841,7 @@ __global__ __launch_bounds__(256, 5) void k_rf_resolve(
   // the parts of the queue: lane q holds the number of entries in the parts up to and including q
   const int q_incl = wave_incl_scan((int)min((long long)max(W.queue[16 * lane], 0), W.qcap));
   const int nq = __builtin_amdgcn_readlane(q_incl, 63);
-  int *lq_tab = W.work + RF_WORK_HDR + 65536, *items = lq_tab + 4 * RF_LQ_CAP;
+  int *lq_tab = W.work + RF_WORK_LQ, *items = W.work + RF_WORK_ITEMS;
   for (int e = wave; e < nq; e += nwaves) {
     const int part = __popcll(__ballot(q_incl <= e));
     const int before = part ? __builtin_amdgcn_readlane(q_incl, part - 1) : 0;
@@ -933,7 +975,7 @@ __global__ __launch_bounds__(256) void k_rf_ranges(
   if (n_used_ptr) { const long long u = *n_used_ptr; n_used = u < n_max ? u : n_max; }
   const int wave = (blockIdx.x * 256 + threadIdx.x) >> 6;
   const int nwaves = (gridDim.x * 256) >> 6;
-  int *lq_tab = W.work + RF_WORK_HDR + 65536, *items = lq_tab + 4 * RF_LQ_CAP;
+  int *lq_tab = W.work + RF_WORK_LQ, *items = W.work + RF_WORK_ITEMS;
   for (int t = wave; t < n_items; t += nwaves) {
     const int lq = items[2 * t];
     const long long rg = items[2 * t + 1];
@@ -1540,9 +1582,12 @@ inline int tile_grid(int64_t pool_cap, int S) {
 
 }  // namespace
 
+// chunk_cnt: the member counts of the LiDAR side, then those of the pseudo side
+static inline int64_t seg_count_words(int64_t V, int cap_item) { return V * DFU3D_MAX_INST * seg_ranges(cap_item); }
+
 extern "C" int64_t dfu3d_segments_scratch_words(int32_t V, int32_t a_cap, int32_t b_cap) {
   if (V <= 0 || a_cap <= 0 || b_cap <= 0) return DFU3D_EINVAL;
-  return (int64_t)V * DFU3D_MAX_INST * ((int64_t)seg_ranges(a_cap) + seg_ranges(b_cap));
+  return seg_count_words(V, a_cap) + seg_count_words(V, b_cap);
 }
 
 extern "C" int dfu3d_segments_build(
@@ -1566,7 +1611,7 @@ extern "C" int dfu3d_segments_build(
   if (shadow && ((uintptr_t)shadow & 15u)) return DFU3D_EINVAL;
   hipStream_t st = (hipStream_t)stream;
   const int nra = seg_ranges(a_cap), nrb = seg_ranges(b_cap);
-  int32_t *rc_a = chunk_cnt, *rc_b = chunk_cnt + (size_t)V * nra * DFU3D_MAX_INST;
+  int32_t *rc_a = chunk_cnt, *rc_b = chunk_cnt + seg_count_words(V, a_cap);
   const int gxa = std::min((nra + SEG_WPB - 1) / SEG_WPB, SEG_GX), gxb = std::min((nrb + SEG_WPB - 1) / SEG_WPB, SEG_GX);
   hipLaunchKernelGGL(k_seg_count, dim3(gxa, V), dim3(SEG_WPB * 64), 0, st, a_bits, a_n, a_cap, nra, rc_a);
   DFU3D_LAUNCH_CHECK();
@@ -1605,20 +1650,14 @@ extern "C" int dfu3d_radius_filter(double *px, double *py, double *pz, const int
   if ((int64_t)S >= (int64_t)RF_NOSEG) return DFU3D_ERANGE;         // 16-bit segment ids in the shadow
   if ((uintptr_t)shadow & 15u) return DFU3D_EINVAL;
   hipStream_t st = (hipStream_t)stream;
-  float4 *pq = (float4 *)shadow;
-  // scratch behind the shadow proper: one record (two boxes, a count) per 512 slots, the ranges' U slots, the
-  // per-segment overflow lists (at the segments' own pool positions), counters, the tables of the long queries
-  const size_t n_ranges = (size_t)((pool_cap + 511) / 512 + 1);
-  RfScratch W;
+  const RfCut C = rf_cut(shadow, pool_cap);
+  if (C.bytes > DFU3D_SHADOW_BYTES(pool_cap) || RF_QHDR + RF_QSHARDS * (int64_t)C.W.qcap > DFU3D_RF_QUEUE_INTS(pool_cap))
+    return DFU3D_ERANGE;                          // (the header's macros no longer cover the cut: see the static_asserts)
+  float4 *pq = C.pq;
+  const int64_t n_ranges = C.n_ranges;
+  RfScratch W = C.W;
   W.flags = flags;
   W.queue = queue;
-  W.qcap = rf_queue_part_cap(pool_cap);
-  W.rrec = (float *)(pq + pool_cap);
-  W.uent = (float4 *)(W.rrec + BOX_FLOATS * n_ranges);
-  W.upos = (uint32_t *)(W.uent + (size_t)RF_WLIST * n_ranges);
-  W.ulist = (float4 *)(W.upos + (size_t)RF_WLIST * n_ranges);
-  W.work = (int *)(W.ulist + pool_cap);
-  W.ucount = W.work + RF_WORK_HDR;
   W.seg_base = (const long long *)seg_base;
   if (phases & DFU3D_RF_SHADOW) {
     // positions outside the given segments carry the "no segment" mark (all bits set)

@@ -227,13 +227,19 @@ def backproject_bin(depth, calib, masks, n_inst, V, max_inst, H, W, geom, table_
 
 
 def shadow_floats(pool_cap):
-    """float32 elements of the radius filter's shadow scratch (DFU3D_SHADOW_BYTES / 4)."""
-    return 8 * pool_cap + (16 + 512 + 128) * ((pool_cap + 511) // 512 + 1) + 9699456 // 4
+    """float32 elements of the radius filter's shadow scratch (dfu3d_rf_shadow_bytes / 4)."""
+    n = int(_lib.lib().dfu3d_rf_shadow_bytes(int(pool_cap)))
+    if n < 0:
+        raise Dfu3dError("dfu3d_rf_shadow_bytes: invalid pool_cap %r" % (pool_cap,))
+    return n // 4
 
 
 def rf_queue_ints(pool_cap):
-    """int32 elements of the radius filter's queue scratch (DFU3D_RF_QUEUE_INTS)."""
-    return 1024 + 64 * (((pool_cap + 2047) // 2048 + 63) // 64) * 2048
+    """int32 elements of the radius filter's queue scratch (dfu3d_rf_queue_ints)."""
+    n = int(_lib.lib().dfu3d_rf_queue_ints(int(pool_cap)))
+    if n < 0:
+        raise Dfu3dError("dfu3d_rf_queue_ints: invalid pool_cap %r" % (pool_cap,))
+    return n
 
 
 def segments_build(a_bits, a_x, a_y, a_z, a_n, a_cap, b_bits, b_x, b_y, b_z, b_n, b_cap, V,

@@ -248,6 +248,11 @@ int dfu3d_radius_filter(double *px, double *py, double *pz,
                         int64_t pool_cap, const int64_t *n_used, void *shadow,
                         int32_t *tile_off, uint8_t *flags,
                         int32_t *queue, int32_t phases, void *stream);
+/* The two size macros are ABI.  Their literals are constants of segment_stage.hip multiplied out, and static_asserts
+ * there tie them to the cut of the scratch (rf_cut): 32 = the shadow's and the overflow lists' 16 B per slot; per range
+ * of 512 slots 64 = BOX_FLOATS floats, 2048 + 512 = RF_WLIST entries of 16 + 4 B; 9699456 = 4 * (RF_WORK_HDR + one
+ * length per segment id + 4 ints per RF_LQ_CAP long queries + 2 ints per RF_ITEM_CAP work items).  Queue: RF_QHDR
+ * counters, RF_QSHARDS parts of whole RF_WG-slot workgroups. */
 #define DFU3D_SHADOW_BYTES(pool_cap) (32 * (int64_t)(pool_cap) + (64 + 2048 + 512) * (((int64_t)(pool_cap) + 511) / 512 + 1) + 9699456)
 /* int32 elements of `queue`: 64 parts (one per 64th of the 2048-slot workgroups) behind their 64 counters */
 #define DFU3D_RF_QUEUE_INTS(pool_cap) (1024 + 64 * ((((int64_t)(pool_cap) + 2047) / 2048 + 63) / 64) * 2048)
