@@ -14,6 +14,8 @@ from fractions import Fraction
 
 import numpy as np
 
+from ._header import CONSTANTS
+
 
 def get_calib_from_file(filepath):
     """calibration_kitti.py:23-58: float32 parse of P2 / P3 / R0_rect /
@@ -187,8 +189,8 @@ class Calibration(object):
         return boxes, np.stack((x, y), axis=2)
 
     def record(self):
-        """48 float32: M43 | P2 | cu cv fu fv tx ty | Minv[:, :3] | pad."""
-        r = np.zeros((48,), np.float32)
+        """DFU3D_CALIB_FLOATS (48) float32: M43 | P2 | cu cv fu fv tx ty | Minv[:, :3] | pad."""
+        r = np.zeros((CONSTANTS["DFU3D_CALIB_FLOATS"],), np.float32)
         r[0:12] = self.M43.reshape(-1)
         r[12:24] = self.P2.reshape(-1)
         r[24:30] = [self.cu, self.cv, self.fu, self.fv, self.tx, self.ty]

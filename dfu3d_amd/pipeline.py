@@ -19,6 +19,7 @@ from typing import List, Optional
 import numpy as np
 import torch
 
+from . import stages as st
 from .calibration import Calibration
 from .engine import PseudoBoxEngine, ViewBatch
 from .labels import write_label_file
@@ -147,7 +148,7 @@ class BatchedLabeler:
 
     def _instance_tensors(self, B, M, items):
         """Per-view small inputs from [(stem, calib record (48,), classes, scores, boxes, thing_classes)]."""
-        calib = torch.zeros((B, 48), dtype=torch.float32)
+        calib = torch.zeros((B, st.CALIB_FLOATS), dtype=torch.float32)
         n_inst = torch.zeros(B, dtype=torch.int32)
         cls = torch.zeros((B, M), dtype=torch.int32)
         car = torch.zeros((B, M), dtype=torch.int32)

@@ -14,20 +14,11 @@ import torch
 from . import _lib
 from ._lib import BinGeom, Dfu3dError
 
-CALIB_FLOATS = 48
-ROW_DOUBLES = 24
-MAX_INST = 32
+# Every integer macro DFU3D_<NAME> of include/dfu3d.h is <NAME> here, with the header's value (read by _header.py, never
+# typed again): CALIB_FLOATS, ROW_DOUBLES, MAX_INST, TABLE_ENTRY_BYTES, MASK_BYTES, BP_*, RF_*, ST_*, STAGE_*, EVAL_MAX_DET,
+# GT_SAMPLE_MAX_BOXES, CENTER_MAX_K, SELFTEST_SCRATCH_BYTES, ...
+globals().update({name[len("DFU3D_"):]: value for name, value in _lib.CONSTANTS.items()})
 
-BP_BIN, BP_AMB, BP_MARK, BP_VOX, BP_REPAIR, BP_ALL = 1, 2, 4, 8, 16, 31
-MASK_BYTES = 0
-RF_SHADOW, RF_FLAGS, RF_RESOLVE, RF_COMPACT, RF_ALL = 1, 2, 4, 8, 15
-
-ST_POOL_OVERFLOW = 1
-ST_VOX_OVERFLOW = 2
-ST_ROW_OVERFLOW = 4
-ST_BIN_RANGE = 8
-ST_VOX_PTS_OVERFLOW = 16
-ST_VOXEL_RANGE = 32
 STATUS_TEXT = {
     ST_POOL_OVERFLOW: "instance point pool too small (raise pool_cap)",
     ST_VOX_OVERFLOW: "more voxels than cap_vox in a view (raise cap_vox; bin table must be re-initialised)",
@@ -35,6 +26,7 @@ STATUS_TEXT = {
     ST_BIN_RANGE: "a spherical bin fell outside the bin table",
     ST_VOX_PTS_OVERFLOW: "overflow-bin pixel list too small",
     ST_VOXEL_RANGE: "voxel_down_sample: a segment is wider than 2^21 voxels along an axis",
+    ST_CENTER_OVERFLOW: "center_assign: more than num_max_objs boxes of one head in one sample",
 }
 
 
@@ -83,9 +75,6 @@ def backproject_scratch_words(V, H, W, cap_vox, max_points, geom):
     if rc != 0:
         raise Dfu3dError("dfu3d_backproject_scratch_words: invalid sizes")
     return a.value, b.value
-
-
-TABLE_ENTRY_BYTES = 28
 
 
 def bin_table_init(table, entries_total):
@@ -424,9 +413,6 @@ def rotate_iou_eval(boxes, query_boxes, criterion=-1):
     return out
 
 
-EVAL_MAX_DET = 2048          # DFU3D_EVAL_MAX_DET: detections per frame the evaluator takes
-
-
 class EvalFrames:
     """All frames of an evaluation as flat CUDA tensors (see include/dfu3d.h, "f-3, AP evaluation"): offsets int64
     (F+1), per-box float64 bbox (.,4), cam (.,7), alpha, score, truncated and int32 code, dontcare, occluded."""
@@ -479,6 +465,9 @@ def _combo_tensor(combos, device):
     return host.to(device)
 
 
+_COMBO_P = ctypes.POINTER(_lib.EvalCombo)     # the header's type of `combos`; what is passed is a DEVICE array, hence the casts
+
+
 def eval_match_scores(fr: EvalFrames, ov, metric, combos):
     """First pass of eval_class for every cell of `combos` -> (matched float64 (n_combo, n_gt) NaN-padded per frame,
     n_valid int32 (n_combo, F))."""
@@ -489,7 +478,7 @@ def eval_match_scores(fr: EvalFrames, ov, metric, combos):
     cb = _combo_tensor(combos, dev)
     rc = _lib.lib().dfu3d_eval_match_scores(
         int(metric), fr.F, fr.max_dt, *fr._off_args(), _chk(ov, "ov", torch.float64, min_numel=max(fr.n_pairs, 1)),
-        *fr._box_args(), _chk(cb, "combos", torch.uint8, numel=16 * C), C, fr.n_gt,
+        *fr._box_args(), ctypes.cast(_chk(cb, "combos", torch.uint8, numel=ctypes.sizeof(_lib.EvalCombo) * C), _COMBO_P), C, fr.n_gt,
         _chk(matched, "matched", torch.float64, min_numel=C * fr.n_gt), _chk(n_valid, "n_valid", torch.int32, numel=C * fr.F),
         _stream())
     _lib.check(rc, "dfu3d_eval_match_scores")
@@ -508,7 +497,7 @@ def eval_match_stats(fr: EvalFrames, ov, metric, combos, thresholds, n_thresh, c
     cb = _combo_tensor(combos, dev)
     rc = _lib.lib().dfu3d_eval_match_stats(
         int(metric), fr.F, fr.max_dt, *fr._off_args(), _chk(ov, "ov", torch.float64, min_numel=max(fr.n_pairs, 1)),
-        *fr._box_args(), _chk(cb, "combos", torch.uint8, numel=16 * C), C,
+        *fr._box_args(), ctypes.cast(_chk(cb, "combos", torch.uint8, numel=ctypes.sizeof(_lib.EvalCombo) * C), _COMBO_P), C,
         _chk(thresholds, "thresholds", torch.float64, numel=C * T), _chk(n_thresh, "n_thresh", torch.int32, numel=C), T,
         1 if compute_aos else 0, _chk(pr, "pr", torch.int64, numel=C * T * 3),
         _chk(sim, "sim", torch.float64, numel=C * fr.F * T) if compute_aos else None, _stream())
@@ -531,9 +520,6 @@ def nms_bev(boxes, thresh, normal=False):
             _chk(num, "num_keep", torch.int32, numel=1), _stream())
     _lib.check(rc, "dfu3d_nms_bev")
     return keep, int(num.item())
-
-
-SELFTEST_SCRATCH_BYTES = 128 + 16 * (65536 + 16384)
 
 
 def selftest_classify(calib_record, H, W, geom, key_axis, n, seed=1, d_lo=0.5, d_hi=120.0, device="cuda:0"):
@@ -613,10 +599,6 @@ def status_message(word):
     return "; ".join(t for b, t in STATUS_TEXT.items() if word & b) or "ok"
 
 
-ST_BOX_RANGE = 64                      # dfu3d_gt_sample_*: a scene beyond the box cap / max_scene_points
-GT_SAMPLE_MAX_BOXES = 512              # DFU3D_GT_SAMPLE_MAX_BOXES
-
-
 def gt_sample_collide(boxes, box_off, gt_cnt, grp, gt_mask, max_boxes, status):
     """Ground-truth sampling, collision step (dfu3d_gt_sample_collide).  boxes float64 (Nt,7), box_off int32 (B+1),
     gt_cnt int32 (B), grp / gt_mask int32 (Nt) -> accept int32 (Nt), out_boxes float64 (Nt,7), out_src int32 (Nt),
@@ -685,11 +667,6 @@ def gt_sample_paste(points, pt_off, max_scene_points, box_off, gt_cnt, boxes, la
         _chk(status, "status", torch.int32, numel=1), _stream())
     _lib.check(rc, "dfu3d_gt_sample_paste")
     return out, out_off
-
-
-ST_CENTER_OVERFLOW = 128               # dfu3d_center_assign: more than num_max_objs boxes of one head in one sample
-CENTER_MAX_K = 1024                    # DFU3D_CENTER_MAX_K
-STATUS_TEXT[ST_CENTER_OVERFLOW] = "center_assign: more than num_max_objs boxes of one head in one sample"
 
 
 def center_assign(gt_boxes, cls_tab, head_plane, n_cls, n_heads, W, H, range_xy, voxel_xy, stride, num_max_objs,

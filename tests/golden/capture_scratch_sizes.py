@@ -56,10 +56,7 @@ def sizes_grid():
 
 def capture(lib_path, kb14_path, commit):
     from dfu3d_amd import _lib
-    libs = {"product": ctypes.CDLL(lib_path), "keybits14": ctypes.CDLL(kb14_path)}
-    for L in libs.values():
-        for sym, (res, args) in _lib.SIGNATURES.items():
-            getattr(L, sym).restype, getattr(L, sym).argtypes = res, args
+    libs = {"product": _lib.bind(ctypes.CDLL(lib_path)), "keybits14": _lib.bind(ctypes.CDLL(kb14_path))}
     L = libs["product"]
     out = {"commit": commit}
     for name, lib in libs.items():

@@ -54,11 +54,7 @@ def main():
     b.pack_masks()                                   # (as `python bench.py`: the masks resident as bit-packed words)
     loaded = {}
     for name, path in libs:
-        L = ctypes.CDLL(path)
-        for sym, (res, a) in _lib.SIGNATURES.items():
-            fn = getattr(L, sym)
-            fn.restype, fn.argtypes = res, a
-        loaded[name] = L
+        loaded[name] = _lib.bind(ctypes.CDLL(path))
     if args.throughput:
         import time
         res = {n: [] for n, _ in libs}
