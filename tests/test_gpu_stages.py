@@ -8,6 +8,8 @@ import pytest
 import torch
 
 from oracle import penet_oracle as O
+from tests import fit_cases as F
+from tests.fit_cases import pool_from_segments as _pool_from_segments
 
 pytestmark = pytest.mark.gpu
 
@@ -39,22 +41,6 @@ def _oracle_calib(c):
 
 
 # ------------------------------------------------------------------ segments helper
-def _pool_from_segments(segs, pad=3):
-    """segs: list of (n_i,3) fp64 arrays -> pool tensors + base/cnt (with gaps)."""
-    base, cnt, chunks, cur = [], [], [], 0
-    for s in segs:
-        base.append(cur)
-        cnt.append(len(s))
-        chunks.append(np.asarray(s, np.float64).reshape(-1, 3))
-        chunks.append(np.full((pad, 3), 777.0))
-        cur += len(s) + pad
-    allp = np.concatenate(chunks) if chunks else np.zeros((0, 3))
-    cap = max(len(allp), 1) + 8
-    P = np.full((cap, 3), 555.0)
-    P[:len(allp)] = allp
-    return P, np.array(base, np.int64), np.array(cnt, np.int32), cap
-
-
 def _clustered_points(rng, n, spread=1.0, outliers=0.05):
     k = max(1, n // 40)
     centers = rng.uniform(-20, 20, (k, 3)) * np.array([1, 1, 0.1])
@@ -382,19 +368,26 @@ def _cluster_cases(rng):
     return cases
 
 
-def test_range_cluster_matches_oracle(st):
+@pytest.mark.parametrize("R0,Rd", [(3.0, 0.001), (3.0, 0.0), (3.0, 0.05), (0.6, 0.001)])
+def test_range_cluster_matches_oracle(st, R0, Rd):
+    """(3.0, 0.001): the reference's radii, every case.  Rd = 0: one radius for all points (the grid's margin is all that
+    keeps cells 3 apart unlinked); Rd = 0.05: R_max is above 4.238 for every case that reaches beyond 25 m, which no grid
+    variant accepts -- the point-level fallback with radii that differ by decimetres; R0 = 0.6: five times as many
+    cells.  The three added pairs leave out the two cases above 29 000 points (the oracle is quadratic)."""
     rng = np.random.default_rng(13)
     cases = _cluster_cases(rng)
+    if (R0, Rd) != (3.0, 0.001):
+        cases = [c for c in cases if len(c) < 29000]
     segs = [np.concatenate([c, np.zeros((len(c), 1))], 1) for c in cases]
     P, base, cnt, cap = _pool_from_segments(segs)
     px, py = _t(P[:, 0]), _t(P[:, 1])
     S = len(segs)
     label = torch.full((cap,), -7, dtype=torch.int32, device=DEV)
-    st.range_cluster(px, py, _t(base), _t(cnt), S, 3.0, 0.001, label, cap)
+    st.range_cluster(px, py, _t(base), _t(cnt), S, R0, Rd, label, cap)
     torch.cuda.synchronize()
     lab = label.cpu().numpy()
     for s, c in enumerate(cases):
-        exp = O.range_cluster_labels(c[:, 0], c[:, 1], 3.0, 0.001)
+        exp = O.range_cluster_labels(c[:, 0], c[:, 1], R0, Rd)
         assert np.array_equal(lab[base[s]:base[s] + len(c)], exp), s
 
 
@@ -406,8 +399,6 @@ def test_lshape_fit_matches_oracle(st):
     p = Params()
     n_theta, dtheta = p.thetas()
     assert n_theta == 89
-    cal = _rand_calib(rng, 30.0)
-    oc = _oracle_calib(cal)
     M = 4
     segs, classes, iscar, boxes = [], [], [], []
     def lshape(cx, cy, L, Wd, yaw, n):
@@ -432,6 +423,8 @@ def test_lshape_fit_matches_oracle(st):
         segs.append(np.zeros((0, 3))); classes.append(0); iscar.append(0); boxes.append([0, 0, 0, 0])
     S = len(segs)
     V = S // M
+    cals = [_rand_calib(rng, (30.0, -55.0, 110.0)[v % 3]) for v in range(V)]      # a calibration per view
+    scores = [0.1 + 0.8 * ((5 * s + 2) % S) / S for s in range(S)]                # a score per instance
     P, base, cnt, cap = _pool_from_segments(segs)
     px, py, pz = _t(P[:, 0]), _t(P[:, 1]), _t(P[:, 2])
     tb, tc = _t(base), _t(cnt)
@@ -441,10 +434,10 @@ def test_lshape_fit_matches_oracle(st):
     rows = torch.zeros(cap_rows * st.ROW_DOUBLES, dtype=torch.float64, device=DEV)
     n_rows = torch.zeros(1, dtype=torch.int32, device=DEV)
     status = torch.zeros(1, dtype=torch.int32, device=DEV)
-    calib = _t(np.stack([cal.record()] * V))
+    calib = _t(np.stack([c.record() for c in cals]))
     st.lshape_fit(px, py, pz, label, tb, tc, S, M, calib, _t(np.array(classes, np.int32)),
                   _t(np.array(iscar, np.int32)), _t(np.array(boxes, np.float32)),
-                  torch.ones(S, dtype=torch.float32, device=DEV), n_theta, dtheta,
+                  _t(np.array(scores, np.float32)), n_theta, dtheta,
                   p.car_aspect_max, torch.zeros(cap, dtype=torch.float64, device=DEV),
                   torch.zeros(cap, dtype=torch.float64, device=DEV),
                   torch.zeros(cap, dtype=torch.int32, device=DEV), cap_rows, rows, n_rows,
@@ -453,16 +446,9 @@ def test_lshape_fit_matches_oracle(st):
     assert int(status.item()) == 0
     n = int(n_rows.item())
     R = rows.view(cap_rows, st.ROW_DOUBLES)[:n].cpu().numpy()
-    R = R[np.lexsort((R[:, 2], R[:, 1], R[:, 0]))]
-    exp = []
-    for s, pts in enumerate(segs):
-        name = "Car" if iscar[s] else "Truck"
-        for r in O.generate_anns(name, pts, classes[s], np.array(boxes[s], np.float32), oc, O.Params(), inst=s % M):
-            exp.append((s // M, s % M, r.cluster, r))
-    assert n == len(exp), (n, len(exp))
-    for got, (v, j, k, r) in zip(R, exp):
-        assert (int(got[0]), int(got[1]), int(got[2]), int(got[3])) == (v, j, k, r.cls)
-        np.testing.assert_allclose(got[4:16], r.as_vector(), rtol=1e-9, atol=1e-9)
+    exp, _ = F.expected_rows(segs, M, classes, iscar, boxes, scores, [_oracle_calib(c) for c in cals], O.Params())
+    assert n == len(exp) and V == 2, (n, len(exp))
+    F.assert_rows_match(R, exp, dtheta)         # all 24 columns: class, box, score, members, heading index, extents, root
 
 
 def test_lshape_fit_heading_ties_are_decided_like_the_reference(st):
@@ -475,8 +461,6 @@ def test_lshape_fit_heading_ties_are_decided_like_the_reference(st):
     rng = np.random.default_rng(41)
     p = Params()
     n_theta, dtheta = p.thetas()
-    cal = _rand_calib(rng, 30.0)
-    oc = _oracle_calib(cal)
     M = 4
 
     def square_grid(k, side, cx, cy):                      # k x k lattice: invariant under 90-degree rotations and mirrors
@@ -512,6 +496,8 @@ def test_lshape_fit_heading_ties_are_decided_like_the_reference(st):
         segs.append(np.zeros((0, 3))); classes.append(0); iscar.append(0); boxes.append([0, 0, 0, 0])
     S = len(segs)
     V = S // M
+    cals = [_rand_calib(rng, (30.0, -55.0, 110.0)[v % 3]) for v in range(V)]      # a calibration per view
+    scores = [0.1 + 0.8 * ((5 * s + 2) % S) / S for s in range(S)]                # a score per instance
     P, base, cnt, cap = _pool_from_segments(segs)
     px, py, pz = _t(P[:, 0]), _t(P[:, 1]), _t(P[:, 2])
     tb, tc = _t(base), _t(cnt)
@@ -521,9 +507,9 @@ def test_lshape_fit_heading_ties_are_decided_like_the_reference(st):
     rows = torch.zeros(cap_rows * st.ROW_DOUBLES, dtype=torch.float64, device=DEV)
     n_rows = torch.zeros(1, dtype=torch.int32, device=DEV)
     status = torch.zeros(1, dtype=torch.int32, device=DEV)
-    st.lshape_fit(px, py, pz, label, tb, tc, S, M, _t(np.stack([cal.record()] * V)), _t(np.array(classes, np.int32)),
+    st.lshape_fit(px, py, pz, label, tb, tc, S, M, _t(np.stack([c.record() for c in cals])), _t(np.array(classes, np.int32)),
                   _t(np.array(iscar, np.int32)), _t(np.array(boxes, np.float32)),
-                  torch.ones(S, dtype=torch.float32, device=DEV), n_theta, dtheta,
+                  _t(np.array(scores, np.float32)), n_theta, dtheta,
                   p.car_aspect_max, torch.zeros(cap, dtype=torch.float64, device=DEV),
                   torch.zeros(cap, dtype=torch.float64, device=DEV),
                   torch.zeros(cap, dtype=torch.int32, device=DEV), cap_rows, rows, n_rows, status, cap)
@@ -531,16 +517,11 @@ def test_lshape_fit_heading_ties_are_decided_like_the_reference(st):
     assert int(status.item()) == 0
     n = int(n_rows.item())
     R = rows.view(cap_rows, st.ROW_DOUBLES)[:n].cpu().numpy()
-    R = R[np.lexsort((R[:, 2], R[:, 1], R[:, 0]))]
-    exp = []
-    for s_, pts in enumerate(segs):
-        for r in O.generate_anns("Truck", pts, classes[s_], np.array(boxes[s_], np.float32), oc, O.Params(), inst=s_ % M):
-            exp.append((s_ // M, s_ % M, r.cluster, r))
-    assert n == len(exp) and n >= 8, (n, len(exp))
-    for got, (v, j, k, r) in zip(R, exp):
-        assert (int(got[0]), int(got[1]), int(got[2])) == (v, j, k)
-        # column 18 of the engine row is the chosen heading: the oracle's (= the reference's) arg-max, exactly
-        np.testing.assert_allclose(got[4:16], r.as_vector(), rtol=1e-9, atol=1e-9)
+    exp, _ = F.expected_rows(segs, M, classes, iscar, boxes, scores, [_oracle_calib(c) for c in cals], O.Params())
+    assert n == len(exp) and n >= 8 and V == 2, (n, len(exp))
+    # column 18 of the engine row is the chosen heading: the oracle's (= the reference's) arg-max, exactly -- compared as
+    # an index, with member count and root equal and the extents within 1e-9 (all 24 columns)
+    F.assert_rows_match(R, exp, dtheta)
 
 
 # ------------------------------------------------------------------ a4/a5/a6
