@@ -7,13 +7,21 @@ than NUM_MAX_OBJS boxes of one head in one sample (where the reference raises) s
 int32 the call resets: `assign_targets(..., check=True)` reads it and raises, otherwise `check_status()` does at the
 caller's next natural synchronisation.
 
-Divergence from the reference: `gt_boxes` is not written (the reference leaves head-local class ids in its last column) and
+`get_loss` is the reference's (center_head.py:229-295) on csrc/centerloss_stage.hip through
+dfu3d_amd.center_loss_ops: all heads in three launches forward and two backward, no float atomics, and one
+device-to-host copy for the tb_dict (none with as_tensors=True).
+
+Divergences from the reference: `pred_dict['hm']` holds raw logits and `get_loss` does not overwrite it (the reference
+replaces it by the clamped sigmoid); a masked-out slot contributes nothing to loss or gradient even where the
+prediction at its cell is not finite (the reference multiplies by the mask and gives NaN), and the same holds for a NaN
+target channel, which is skipped (the reference's `isnotnan` multiplies NaN by zero); the IoU branches raise
+NotImplementedError; `gt_boxes` is not written (the reference leaves head-local class ids in its last column) and
 boxes are assigned by the caller's original class ids."""
 import numpy as np
 import torch
 
 from . import centernet_utils, model_nms_utils
-from .. import stages
+from .. import center_loss_ops, stages
 from .._lib import Dfu3dError
 
 
@@ -52,6 +60,7 @@ class CenterHead:
         self.status = torch.zeros(1, dtype=torch.int32, device=self.device)
         head_cfg = _get(model_cfg, 'SEPARATE_HEAD_CFG', None)
         self.head_order = list(_get(head_cfg, 'HEAD_ORDER')) if head_cfg is not None else ['center', 'center_z', 'dim', 'rot']
+        self.forward_ret_dict = {}
 
     def check_status(self):
         """Raise if the last assign_targets met more than NUM_MAX_OBJS boxes of one head in one sample (one host read)."""
@@ -137,3 +146,25 @@ class CenterHead:
             ret_dict[k]['pred_scores'] = torch.cat(ret_dict[k]['pred_scores'], dim=0)
             ret_dict[k]['pred_labels'] = torch.cat(ret_dict[k]['pred_labels'], dim=0) + 1
         return ret_dict
+
+    def get_loss(self, pred_dicts=None, target_dicts=None, as_tensors=False):
+        """center_head.py:229-295.  pred_dicts: per head {'hm': logits (B, n_cls, H, W), HEAD_ORDER's maps}; target_dicts:
+        what assign_targets returns; both default to self.forward_ret_dict's.  Returns (loss, tb_dict): loss a
+        differentiable 0-dim tensor, tb_dict with 'hm_loss_head_%d', 'loc_loss_head_%d' and 'rpn_loss' as Python floats
+        read with one copy, or, with as_tensors=True, as 0-dim views of the device vector without any synchronisation."""
+        pred_dicts = self.forward_ret_dict['pred_dicts'] if pred_dicts is None else pred_dicts
+        target_dicts = self.forward_ret_dict['target_dicts'] if target_dicts is None else target_dicts
+        if _get(self.model_cfg, 'IOU_REG_LOSS', False) or any('iou' in d for d in pred_dicts):
+            raise NotImplementedError("CenterHead.get_loss: the IoU branches ('iou' head, IOU_REG_LOSS) are not supported")
+        weights = _get(_get(self.model_cfg, 'LOSS_CONFIG'), 'LOSS_WEIGHTS')
+        losses, _ = center_loss_ops.center_loss(
+            [d['hm'] for d in pred_dicts], target_dicts['heatmaps'], [[d[name] for name in self.head_order] for d in pred_dicts],
+            target_dicts['target_boxes'], target_dicts['inds'], target_dicts['masks'], cls_weight=weights['cls_weight'],
+            loc_weight=weights['loc_weight'], code_weights=list(weights['code_weights']))
+        values = losses.detach() if as_tensors else losses.tolist()          # tolist: the call's one copy to the host
+        tb_dict = {}
+        for idx in range(len(pred_dicts)):
+            tb_dict['hm_loss_head_%d' % idx] = values[2 * idx]
+            tb_dict['loc_loss_head_%d' % idx] = values[2 * idx + 1]
+        tb_dict['rpn_loss'] = values[-1]
+        return losses[-1], tb_dict
