@@ -22,7 +22,7 @@ _LITERAL = re.compile(r"(0|[1-9]\d*)[uU]?")
 _OPS = set("+-*()")
 
 
-def _ctype(decl, structs, where, ret=False):
+def _ctype(decl, structs, where, ret=False, scalars=SCALARS):
     m = _DECL.fullmatch(decl.strip())
     base, ptr = m.groups() if m else (None, None)
     if base in structs:
@@ -31,8 +31,8 @@ def _ctype(decl, structs, where, ret=False):
         return ctypes.c_char_p
     if ptr and base in _POINTEES:
         return ctypes.c_void_p
-    if not ptr and base in SCALARS:
-        return SCALARS[base]
+    if not ptr and base in scalars:
+        return scalars[base]
     raise ValueError("dfu3d.h: %s: unknown type in %r" % (where, decl.strip()))
 
 
@@ -74,10 +74,12 @@ def _int_expr(body):
     return v
 
 
-def parse(text):
+def parse(text, more_scalars=None):
     """Header text -> (structs {C name: Structure class}, signatures {name: (restype, [argtypes])}, constants
-    {DFU3D_NAME: int}).  Function-like macros, the include guard and macros whose body is no integer expression are
-    skipped (the library's size functions answer for DFU3D_SHADOW_BYTES / DFU3D_RF_QUEUE_INTS)."""
+    {DFU3D_NAME: int}).  more_scalars: {C name: ctypes type} a header other than dfu3d.h passes by value in its prototypes
+    on top of SCALARS (dfu3d_post.h: size_t); dfu3d.h itself stays within SCALARS.  Function-like macros, the include
+    guard and macros whose body is no integer expression are skipped (the library's size functions answer for
+    DFU3D_SHADOW_BYTES / DFU3D_RF_QUEUE_INTS)."""
     text = re.sub(r"/\*.*?\*/", " ", text, flags=re.S)
     constants = {}
     for name, params, body in re.findall(r"(?m)^[ \t]*#[ \t]*define[ \t]+(DFU3D_\w+)(\(?)(.*)$", text):
@@ -101,6 +103,7 @@ def parse(text):
                 fields.append((field, _ctype(ctype, structs, name)))
         structs[name] = type(name, (ctypes.Structure,), {"_fields_": fields, "__doc__": "%s (include/dfu3d.h)." % name})
     signatures = {}
+    scalars = dict(SCALARS, **(more_scalars or {}))
     text = re.sub(r'extern\s+"C"\s*\{|\}', "", struct_re.sub("", text))
     for decl in filter(None, (d.strip() for d in text.split(";"))):
         m = re.fullmatch(r"(.+?)\b(dfu3d_\w+)\s*\((.*)\)", decl, re.S)
@@ -108,7 +111,8 @@ def parse(text):
             raise ValueError("dfu3d.h: cannot read the declaration %r" % decl)
         ret, name, args = m.groups()
         args = [] if args.strip() == "void" else args.split(",")
-        signatures[name] = (_ctype(ret, structs, name, ret=True), [_ctype(a, structs, name) for a in args])
+        signatures[name] = (_ctype(ret, structs, name, ret=True, scalars=scalars),
+                            [_ctype(a, structs, name, scalars=scalars) for a in args])
     return structs, signatures, constants
 
 

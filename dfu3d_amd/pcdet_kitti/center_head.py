@@ -7,6 +7,9 @@ than NUM_MAX_OBJS boxes of one head in one sample (where the reference raises) s
 int32 the call resets: `assign_targets(..., check=True)` reads it and raises, otherwise `check_status()` does at the
 caller's next natural synchronisation.
 
+`generate_predicted_boxes_batched` is the inference end for a whole batch on csrc/postproc_stage.hip: the decode of
+every head into one block, one segmented NMS and one gather, with one host read (none with as_padded=True).
+
 `get_loss` is the reference's (center_head.py:229-295) on csrc/centerloss_stage.hip through
 dfu3d_amd.center_loss_ops: all heads in three launches forward and two backward, no float atomics, and one
 device-to-host copy for the tb_dict (none with as_tensors=True).
@@ -58,6 +61,12 @@ class CenterHead:
         self._cls_tab = torch.from_numpy(tab).to(self.device)
         self._head_plane = torch.tensor(plane, dtype=torch.int32, device=self.device)
         self.status = torch.zeros(1, dtype=torch.int32, device=self.device)
+        # class id within a head -> 0-based id over class_names (generate_predicted_boxes_batched); unused slots 0
+        post_map = np.zeros((len(self.class_names_each_head), max(1, max(len(x) for x in self.class_names_each_head))), np.int32)
+        for h, names in enumerate(self.class_names_each_head):
+            post_map[h, :len(names)] = [self.class_names.index(x) for x in names]
+        self._post_cls_map = torch.from_numpy(post_map).to(self.device)
+        self._post_limit = (None, None)
         head_cfg = _get(model_cfg, 'SEPARATE_HEAD_CFG', None)
         self.head_order = list(_get(head_cfg, 'HEAD_ORDER')) if head_cfg is not None else ['center', 'center_z', 'dim', 'rot']
         self.forward_ret_dict = {}
@@ -146,6 +155,70 @@ class CenterHead:
             ret_dict[k]['pred_scores'] = torch.cat(ret_dict[k]['pred_scores'], dim=0)
             ret_dict[k]['pred_labels'] = torch.cat(ret_dict[k]['pred_labels'], dim=0) + 1
         return ret_dict
+
+    def generate_predicted_boxes_batched(self, batch_size, pred_dicts, as_padded=False):
+        """`generate_predicted_boxes` for all heads and samples in one launch chain: per head the sigmoid / exp and the
+        decode kernel writing into one (n_heads, B, K, C) block, then ONE segmented NMS over the n_heads * B row lists
+        (stages.nms_bev_segments: the decode's rows are in descending score order already, nothing is sorted again) and
+        ONE gather of the survivors (stages.center_collect).  Returns the list `generate_predicted_boxes` returns -- views
+        of the padded tensors cut after one host read of the B row counts -- or, with as_padded=True, the dict
+        {'pred_boxes' (B, out_cap, C), 'pred_scores', 'pred_labels' (B, out_cap), 'count' int32 (B)} without any
+        synchronisation; rows at or beyond count[b] are 0.  Where scores tie, the decode's order (ascending flat index)
+        decides; `generate_predicted_boxes` leaves ties to torch.topk / argsort.  class_specific_nms, circle_nms, IoU
+        rectification and an 'iou' head raise NotImplementedError: `generate_predicted_boxes` is the path for them."""
+        post_process_cfg = _get(self.model_cfg, 'POST_PROCESSING')
+        nms_cfg = _get(post_process_cfg, 'NMS_CONFIG')
+        nms_type = _get(nms_cfg, 'NMS_TYPE')
+        if nms_type not in ('nms_gpu', 'nms_normal_gpu'):
+            raise NotImplementedError("generate_predicted_boxes_batched: NMS_TYPE %r (use generate_predicted_boxes)" % (nms_type,))
+        if _get(post_process_cfg, 'USE_IOU_TO_RECTIFY_SCORE', False):
+            raise NotImplementedError("generate_predicted_boxes_batched: USE_IOU_TO_RECTIFY_SCORE reorders the scores "
+                                      "after the decode (use generate_predicted_boxes)")
+        if any('iou' in d for d in pred_dicts):
+            raise NotImplementedError("generate_predicted_boxes_batched: an 'iou' head (use generate_predicted_boxes)")
+        K = _get(post_process_cfg, 'MAX_OBJ_PER_SAMPLE')
+        if isinstance(K, (list, tuple)):
+            if len(set(int(k) for k in K)) != 1:
+                raise NotImplementedError("generate_predicted_boxes_batched: heads with different MAX_OBJ_PER_SAMPLE %s "
+                                          "(use generate_predicted_boxes)" % (list(K),))
+            K = K[0]
+        K = int(K)
+        n_heads, B = len(pred_dicts), int(batch_size)
+        if n_heads != len(self.class_names_each_head):
+            raise Dfu3dError("generate_predicted_boxes_batched: %d pred_dicts for %d heads"
+                             % (n_heads, len(self.class_names_each_head)))
+        if any(int(d['hm'].shape[0]) != B for d in pred_dicts):
+            raise Dfu3dError("generate_predicted_boxes_batched: a heat map's batch differs from batch_size = %d" % B)
+        with_vel = 'vel' in self.head_order
+        nb = 9 if with_vel else 7
+        dev = pred_dicts[0]['hm'].device
+        limit_key = (tuple(float(v) for v in _get(post_process_cfg, 'POST_CENTER_LIMIT_RANGE')), dev)
+        if self._post_limit[0] != limit_key:                # a host-to-device copy synchronises: once per range, not per call
+            self._post_limit = (limit_key, torch.tensor(limit_key[0], dtype=torch.float32, device=dev))
+        limit = self._post_limit[1]
+        boxes = torch.empty((n_heads, B, K, nb), dtype=torch.float32, device=dev)
+        scores = torch.empty((n_heads, B, K), dtype=torch.float32, device=dev)
+        labels = torch.empty((n_heads, B, K), dtype=torch.int32, device=dev)
+        count = torch.empty((n_heads, B), dtype=torch.int32, device=dev)
+        for idx, pred_dict in enumerate(pred_dicts):
+            centernet_utils.decode_raw(
+                heatmap=pred_dict['hm'].sigmoid(), rot_cos=pred_dict['rot'][:, 0].unsqueeze(dim=1),
+                rot_sin=pred_dict['rot'][:, 1].unsqueeze(dim=1), center=pred_dict['center'],
+                center_z=pred_dict['center_z'], dim=pred_dict['dim'].exp(), vel=pred_dict['vel'] if with_vel else None,
+                point_cloud_range=self.point_cloud_range, voxel_size=self.voxel_size,
+                feature_map_stride=self.feature_map_stride, K=K, score_thresh=_get(post_process_cfg, 'SCORE_THRESH'),
+                post_center_limit_range=limit, out=(boxes[idx], scores[idx], labels[idx], None, count[idx]))
+        post_max = int(_get(nms_cfg, 'NMS_POST_MAXSIZE'))
+        keep, num_keep = stages.nms_bev_segments(
+            boxes.view(n_heads * B, K, nb), count.view(-1), float(_get(nms_cfg, 'NMS_THRESH')),
+            pre_max=int(_get(nms_cfg, 'NMS_PRE_MAXSIZE')), post_max=post_max, normal=(nms_type == 'nms_normal_gpu'))
+        out_cap = n_heads * (min(K, post_max) if post_max > 0 else K)
+        out_boxes, out_scores, out_labels, out_count = stages.center_collect(
+            boxes, scores, labels, keep, num_keep, self._post_cls_map, out_cap)
+        if as_padded:
+            return {'pred_boxes': out_boxes, 'pred_scores': out_scores, 'pred_labels': out_labels, 'count': out_count}
+        return [{'pred_boxes': out_boxes[k, :n], 'pred_scores': out_scores[k, :n], 'pred_labels': out_labels[k, :n]}
+                for k, n in enumerate(out_count.tolist())]          # tolist: the call's one copy to the host
 
     def get_loss(self, pred_dicts=None, target_dicts=None, as_tensors=False):
         """center_head.py:229-295.  pred_dicts: per head {'hm': logits (B, n_cls, H, W), HEAD_ORDER's maps}; target_dicts:

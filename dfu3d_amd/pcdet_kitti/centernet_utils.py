@@ -31,9 +31,9 @@ def _f32(v):
 
 
 def decode_raw(heatmap, rot_cos, rot_sin, center, center_z, dim, point_cloud_range, voxel_size, feature_map_stride,
-               vel=None, iou=None, K=100, circle_nms=False, score_thresh=None, post_center_limit_range=None):
+               vel=None, iou=None, K=100, circle_nms=False, score_thresh=None, post_center_limit_range=None, out=None):
     """The kernel's padded result: boxes (B,K,7|9), scores (B,K), labels int32 (B,K), iou (B,K) | None, count int32 (B),
-    all on the device and without a host read."""
+    all on the device and without a host read.  out: the same tuple preallocated (stages.center_decode) to write into."""
     if circle_nms:
         raise NotImplementedError("decode_bbox_from_heatmap: circle_nms is 'not checked yet' in the reference (assert False)")
     if post_center_limit_range is None:
@@ -53,7 +53,8 @@ def decode_raw(heatmap, rot_cos, rot_sin, center, center_z, dim, point_cloud_ran
     c = lambda t: None if t is None else t.float().contiguous()   # noqa: E731
     return stages.center_decode(c(heatmap), c(rot_cos), c(rot_sin), c(center), c(center_z), c(dim), c(vel), c(iou), K,
                                 (_f32(point_cloud_range[0]), _f32(point_cloud_range[1])),
-                                (_f32(voxel_size[0]), _f32(voxel_size[1])), int(feature_map_stride), limit, score_thresh)
+                                (_f32(voxel_size[0]), _f32(voxel_size[1])), int(feature_map_stride), limit, score_thresh,
+                                out=out)
 
 
 def decode_bbox_from_heatmap(heatmap, rot_cos, rot_sin, center, center_z, dim,

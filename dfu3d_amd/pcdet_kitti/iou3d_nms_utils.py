@@ -61,3 +61,12 @@ def nms_gpu(boxes, scores, thresh, pre_maxsize=None, **kwargs):
 def nms_normal_gpu(boxes, scores, thresh, **kwargs):
     """NMS on the axis-aligned footprints (headings ignored)   (:138-152)."""
     return _nms(boxes, scores, thresh, None, normal=True)
+
+
+def nms_gpu_segments(boxes, counts, thresh, pre_maxsize=None, post_max_size=None):
+    """Rotated NMS of many box lists at once.  boxes (S, cap, C >= 7) float32, the rows of every list ALREADY IN DESCENDING
+    SCORE ORDER (nothing is sorted here; equal scores keep the order they arrive in); counts int32 (S) on the device, the
+    valid rows of each list.  -> (keep int32 (S, cap): positions of the survivors of list s, best first, then -1;
+    num_keep int32 (S)).  Of each list only the first pre_maxsize rows are considered and at most post_max_size kept.
+    One launch chain for all lists and no host read (stages.nms_bev_segments)."""
+    return st.nms_bev_segments(boxes, counts, float(thresh), pre_max=pre_maxsize, post_max=post_max_size)

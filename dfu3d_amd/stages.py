@@ -11,7 +11,7 @@ from dataclasses import dataclass
 
 import torch
 
-from . import _lib
+from . import _lib, _lib_post
 from ._lib import BinGeom, Dfu3dError
 
 # Every integer macro DFU3D_<NAME> of include/dfu3d.h is <NAME> here, with the header's value (read by _header.py, never
@@ -698,10 +698,11 @@ def center_assign(gt_boxes, cls_tab, head_plane, n_cls, n_heads, W, H, range_xy,
 
 
 def center_decode(heat, rot_cos, rot_sin, center, center_z, dim, vel, iou, K, range_xy, voxel_xy, stride, limit,
-                  score_thresh):
+                  score_thresh, out=None):
     """Top-K decode of a batch of head outputs (dfu3d_center_decode).  heat float32 (B,n_cls,H,W) and the regression
     maps -> boxes float32 (B,K,7|9), scores (B,K), labels int32 (B,K), iou (B,K) or None, count int32 (B); the first
-    count[b] rows of sample b are valid."""
+    count[b] rows of sample b are valid.  out: (boxes, scores, labels, iou_out, count) preallocated, contiguous views
+    of those shapes to write into (iou_out None without `iou`); they are what is returned."""
     if heat.dim() != 4:
         raise Dfu3dError("center_decode: heatmap must be (B, n_cls, H, W)")
     B, n_cls, H, W = (int(v) for v in heat.shape)
@@ -709,13 +710,27 @@ def center_decode(heat, rot_cos, rot_sin, center, center_z, dim, vel, iou, K, ra
         raise Dfu3dError("center_decode: K = %d, at most %d" % (K, CENTER_MAX_K))
     dev = heat.device
     nb = 9 if vel is not None else 7
-    boxes = torch.empty((B, K, nb), dtype=torch.float32, device=dev)
-    scores = torch.empty((B, K), dtype=torch.float32, device=dev)
-    labels = torch.empty((B, K), dtype=torch.int32, device=dev)
-    iou_out = torch.empty((B, K), dtype=torch.float32, device=dev) if iou is not None else None
-    count = torch.zeros(max(B, 1), dtype=torch.int32, device=dev)
-    if B == 0:
-        return boxes, scores, labels, iou_out, count[:0]
+    if out is not None:
+        boxes, scores, labels, iou_out, count = out
+        if iou is None:
+            iou_out = None
+        elif iou_out is None:
+            raise Dfu3dError("center_decode: out has no iou_out for the given iou map")
+        for t, name, dtype, n in ((boxes, "boxes", torch.float32, B * K * nb), (scores, "scores", torch.float32, B * K),
+                                  (labels, "labels", torch.int32, B * K), (iou_out, "iou_out", torch.float32, B * K),
+                                  (count, "count", torch.int32, B)):
+            if t is not None:
+                _chk(t, "out." + name, dtype, numel=n)
+        if B == 0:
+            return boxes, scores, labels, iou_out, count
+    else:
+        boxes = torch.empty((B, K, nb), dtype=torch.float32, device=dev)
+        scores = torch.empty((B, K), dtype=torch.float32, device=dev)
+        labels = torch.empty((B, K), dtype=torch.int32, device=dev)
+        iou_out = torch.empty((B, K), dtype=torch.float32, device=dev) if iou is not None else None
+        count = torch.zeros(max(B, 1), dtype=torch.int32, device=dev)
+        if B == 0:
+            return boxes, scores, labels, iou_out, count[:0]
     hw = B * H * W
     rc = _lib.lib().dfu3d_center_decode(
         _chk(heat, "heatmap", torch.float32), _chk(rot_cos, "rot_cos", torch.float32, numel=hw),
@@ -730,3 +745,61 @@ def center_decode(heat, rot_cos, rot_sin, center, center_z, dim, vel, iou, K, ra
         None if iou_out is None else _chk(iou_out, "iou_out", torch.float32), _chk(count, "count", torch.int32), _stream())
     _lib.check(rc, "dfu3d_center_decode")
     return boxes, scores, labels, iou_out, count
+
+
+POST_MAX_CAP = _lib_post.CONSTANTS["DFU3D_POST_MAX_CAP"]
+
+
+def nms_bev_segments(boxes, count, thresh, pre_max=None, post_max=None, normal=False):
+    """Rotated NMS of S box lists in one launch chain (dfu3d_nms_bev_segments).  boxes float32 (S, cap, C >= 7), the rows
+    of a segment in descending score order; count int32 (S) on the device: the rows of each segment that are valid.
+    -> keep int32 (S, cap): the kept positions ascending, then -1; num_keep int32 (S).  No host read."""
+    if boxes.dim() != 3 or boxes.shape[2] < 7:
+        raise Dfu3dError("nms_bev_segments: boxes must be (S, cap, C >= 7), got %s" % (tuple(boxes.shape),))
+    S, cap, C = (int(v) for v in boxes.shape)
+    if cap > POST_MAX_CAP:
+        raise Dfu3dError("nms_bev_segments: cap = %d, at most %d (DFU3D_ERANGE)" % (cap, POST_MAX_CAP))
+    dev = boxes.device
+    keep = torch.empty((S, cap), dtype=torch.int32, device=dev)
+    num = torch.empty(S, dtype=torch.int32, device=dev)
+    b_p = _chk(boxes, "boxes", torch.float32)
+    c_p = _chk(count, "count", torch.int32, numel=S)
+    if S == 0 or cap == 0:
+        return keep, num.zero_()
+    L = _lib_post.lib()
+    nbytes = int(L.dfu3d_nms_segments_scratch_bytes(S, cap))
+    scratch = torch.empty(max(nbytes, 8), dtype=torch.uint8, device=dev)
+    rc = L.dfu3d_nms_bev_segments(b_p, S, cap, C, c_p, ctypes.c_float(thresh), int(pre_max or 0), int(post_max or 0),
+                                  1 if normal else 0, ctypes.c_void_p(scratch.data_ptr()), nbytes,
+                                  _chk(keep, "keep", torch.int32), _chk(num, "num_keep", torch.int32), _stream())
+    _lib.check(rc, "dfu3d_nms_bev_segments")
+    return keep, num
+
+
+def center_collect(boxes, scores, labels, keep, num_keep, cls_map, out_cap):
+    """The survivors of all heads per sample (dfu3d_center_collect).  boxes float32 (n_heads, B, cap, C), scores float32 and
+    labels int32 (n_heads, B, cap), keep (n_heads * B, cap) and num_keep (n_heads * B) of nms_bev_segments, cls_map int32
+    (n_heads, max_cls) -> out_boxes (B, out_cap, C), out_scores (B, out_cap), out_labels int64 (B, out_cap), out_count
+    int32 (B); rows at or beyond out_count[b] are 0.  No host read."""
+    if boxes.dim() != 4:
+        raise Dfu3dError("center_collect: boxes must be (n_heads, B, cap, C), got %s" % (tuple(boxes.shape),))
+    n_heads, B, cap, C = (int(v) for v in boxes.shape)
+    if cls_map.dim() != 2 or cls_map.shape[0] != n_heads or cls_map.shape[1] < 1:
+        raise Dfu3dError("center_collect: cls_map must be (n_heads, max_cls >= 1), got %s" % (tuple(cls_map.shape),))
+    dev = boxes.device
+    S, out_cap = n_heads * B, int(out_cap)
+    out_boxes = torch.empty((B, out_cap, C), dtype=torch.float32, device=dev)
+    out_scores = torch.empty((B, out_cap), dtype=torch.float32, device=dev)
+    out_labels = torch.empty((B, out_cap), dtype=torch.int64, device=dev)
+    out_count = torch.empty(B, dtype=torch.int32, device=dev)
+    if B == 0:
+        return out_boxes, out_scores, out_labels, out_count
+    rc = _lib_post.lib().dfu3d_center_collect(
+        _chk(boxes, "boxes", torch.float32), _chk(scores, "scores", torch.float32, numel=S * cap),
+        _chk(labels, "labels", torch.int32, numel=S * cap), _chk(keep, "keep", torch.int32, numel=S * cap),
+        _chk(num_keep, "num_keep", torch.int32, numel=S), n_heads, B, cap, C, _chk(cls_map, "cls_map", torch.int32),
+        int(cls_map.shape[1]), out_cap, _chk(out_boxes, "out_boxes", torch.float32),
+        _chk(out_scores, "out_scores", torch.float32), _chk(out_labels, "out_labels", torch.int64),
+        _chk(out_count, "out_count", torch.int32), _stream())
+    _lib.check(rc, "dfu3d_center_collect")
+    return out_boxes, out_scores, out_labels, out_count

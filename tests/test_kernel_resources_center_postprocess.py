@@ -1,0 +1,33 @@
+"""CPU-only guard on the CenterHead post-processing kernels (postproc_stage.hip): the gfx950 code object hipcc makes with
+the product's flags uses no scratch memory and spills no registers, and the LDS of every kernel fits a 64 KiB workgroup."""
+import os
+import shutil
+
+import pytest
+
+from tools import isa_mix as tools  # noqa: E402
+
+HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
+SRC = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "dfu3d_amd", "csrc", "postproc_stage.hip")
+FIELDS = ("vgpr_spill_count", "sgpr_spill_count", "private_segment_fixed_size", "group_segment_fixed_size")
+WITH_LDS = {"k_pp_mask", "k_pp_walk"}
+NO_LDS = {"k_pp_collect"}
+
+
+@pytest.mark.skipif(not (os.path.exists(HIPCC) or shutil.which("hipcc")), reason="hipcc not available")
+def test_center_postprocess_kernels_no_scratch_no_spills():
+    found = {}
+    for name, (_, block) in tools.kernels(tools.assembly(SRC)).items():
+        d = tools.demangle(name)
+        short = d.split("(")[0].split("::")[-1].replace("void ", "").strip()
+        if short.startswith("k_pp_"):
+            found[short] = block
+    assert set(found) == WITH_LDS | NO_LDS, sorted(found)
+    for k, block in found.items():
+        res = {f: tools.field(block, f) for f in FIELDS}
+        assert res["vgpr_spill_count"] == 0 and res["private_segment_fixed_size"] == 0, (k, res)
+        assert res["sgpr_spill_count"] == 0, (k, res)
+        if k in WITH_LDS:
+            assert 0 < res["group_segment_fixed_size"] <= 65536, (k, res)
+        else:
+            assert res["group_segment_fixed_size"] == 0, (k, res)
