@@ -1,0 +1,115 @@
+"""Row f-10: OpenPCDet's DataProcessor for the dynamic-pillar CenterPoint configuration --
+`mask_points_and_boxes_outside_range`, `shuffle_points`, `transform_points_to_voxels_placeholder` -- with the range
+masks on the GPU (dfu3d_world_aug_collate, include/dfu3d_aug.h).
+
+Reference: pcdet/datasets/processor/data_processor.py (`__init__` :64-77, :79-115), common_utils.mask_points_by_range,
+box_utils.mask_boxes_outside_range_numpy.
+
+`forward(data_dict)` is the per-scene form, NumPy in and out; the batched form is data_augmentor.prepare_batch, which
+asks this object for the range and for what to mask.  Divergences: `transform_points_to_voxels`
+and every other entry raise NotImplementedError at construction (the voxels of this configuration are made by
+DynamicPillarVFE on the device); USE_CENTER_TO_FILTER false raises; the batched form does not shuffle.
+"""
+from functools import partial
+
+import numpy as np
+import torch
+
+from .. import stages as st
+from .._lib import Dfu3dError
+
+SUPPORTED = ('mask_points_and_boxes_outside_range', 'shuffle_points', 'transform_points_to_voxels_placeholder')
+
+
+class DataProcessor(object):
+    def __init__(self, processor_configs, point_cloud_range, training, num_point_features, device="cuda:0"):
+        self.point_cloud_range = np.asarray(point_cloud_range)
+        if self.point_cloud_range.shape != (6,):
+            raise Dfu3dError("DataProcessor: point_cloud_range must have 6 values")
+        self.training = training
+        self.num_point_features = num_point_features
+        self.mode = 'train' if training else 'test'
+        self.grid_size = self.voxel_size = None
+        self.device = torch.device(device)
+        self.data_processor_queue = []
+        self._mask_cfg = None
+        self._range = None
+        for cur_cfg in processor_configs:
+            name = cur_cfg['NAME']
+            if name not in SUPPORTED:
+                raise NotImplementedError("DataProcessor: the entry %r is not supported" % (name,))
+            self.data_processor_queue.append(getattr(self, name)(config=cur_cfg))
+
+    # ---- what the batched form asks ----
+    def mask_mode(self):
+        """The `mode` bits of dfu3d_world_aug_collate this processor's configuration stands for."""
+        if self._mask_cfg is None:
+            return 0
+        boxes = self._mask_cfg.get('REMOVE_OUTSIDE_BOXES', False) and self.training
+        return st.AUG_MASK_POINTS | (st.AUG_MASK_BOXES if boxes else 0)
+
+    def range_tensor(self):
+        if self._range is None:
+            self._range = torch.from_numpy(self.point_cloud_range.astype(np.float32)).to(self.device)
+        return self._range
+
+    # ---- the entries ----
+    def mask_points_and_boxes_outside_range(self, data_dict=None, config=None):
+        if data_dict is None:
+            if not config.get('USE_CENTER_TO_FILTER', True):
+                raise NotImplementedError("mask_points_and_boxes_outside_range: USE_CENTER_TO_FILTER false (the corner "
+                                          "test) is not supported")
+            self._mask_cfg = config
+            return partial(self.mask_points_and_boxes_outside_range, config=config)
+        points, boxes = data_dict.get('points', None), data_dict.get('gt_boxes', None)
+        mask_boxes = boxes is not None and config['REMOVE_OUTSIDE_BOXES'] and self.training
+        if points is None and not mask_boxes:
+            return data_dict
+        dev = self.device
+        if points is None:
+            points = np.zeros((0, 3), np.float32)
+        if points.ndim != 2 or points.dtype != np.float32 or points.shape[1] < 3:
+            raise Dfu3dError("mask_points_and_boxes_outside_range: points must be (n, C >= 3) float32")
+        if mask_boxes:
+            if boxes.ndim != 2 or boxes.shape[1] < 7 or boxes.dtype not in (np.float32, np.float64):
+                raise Dfu3dError("mask_points_and_boxes_outside_range: gt_boxes must be (N, >= 7) float32 or float64")
+            b7 = np.ascontiguousarray(boxes[:, 0:7])
+        else:
+            b7 = np.zeros((0, 7), np.float32)
+        n, m = points.shape[0], b7.shape[0]
+
+        def h2d(a):
+            return torch.from_numpy(np.ascontiguousarray(a)).to(dev)
+        status = torch.zeros(1, dtype=torch.int32, device=dev)
+        out, n_kept, _, _, _, _, keep = st.world_aug_collate(
+            h2d(points), h2d(np.array([0, n], np.int64)), h2d(b7), h2d(np.array([0, m], np.int32)),
+            h2d(np.array([m], np.int32)), torch.ones(m, dtype=torch.int32, device=dev),
+            h2d(st.aug_params([{'flags': 0}])), self.range_tensor(),
+            st.AUG_MASK_POINTS | (st.AUG_MASK_BOXES if mask_boxes else 0), m, status, want_keep=True)
+        if data_dict.get('points', None) is not None:
+            data_dict['points'] = out[:int(n_kept.item()), 1:].cpu().numpy()
+        if mask_boxes:
+            data_dict['gt_boxes'] = boxes[keep.cpu().numpy() != 0]
+        return data_dict
+
+    def shuffle_points(self, data_dict=None, config=None):
+        if data_dict is None:
+            return partial(self.shuffle_points, config=config)
+        if config['SHUFFLE_ENABLED'][self.mode]:
+            points = data_dict['points']
+            shuffle_idx = np.random.permutation(points.shape[0])
+            data_dict['points'] = points[shuffle_idx]
+        return data_dict
+
+    def transform_points_to_voxels_placeholder(self, data_dict=None, config=None):
+        if data_dict is None:
+            grid_size = (self.point_cloud_range[3:6] - self.point_cloud_range[0:3]) / np.array(config['VOXEL_SIZE'])
+            self.grid_size = np.round(grid_size).astype(np.int64)
+            self.voxel_size = config['VOXEL_SIZE']
+            return partial(self.transform_points_to_voxels_placeholder, config=config)
+        return data_dict
+
+    def forward(self, data_dict):
+        for cur_processor in self.data_processor_queue:
+            data_dict = cur_processor(data_dict=data_dict)
+        return data_dict

@@ -11,7 +11,7 @@ from dataclasses import dataclass
 
 import torch
 
-from . import _lib, _lib_post
+from . import _lib, _lib_aug, _lib_post
 from ._lib import BinGeom, Dfu3dError
 
 # Every integer macro DFU3D_<NAME> of include/dfu3d.h is <NAME> here, with the header's value (read by _header.py, never
@@ -803,3 +803,96 @@ def center_collect(boxes, scores, labels, keep, num_keep, cls_map, out_cap):
         _chk(out_count, "out_count", torch.int32), _stream())
     _lib.check(rc, "dfu3d_center_collect")
     return out_boxes, out_scores, out_labels, out_count
+
+
+# Every integer macro DFU3D_AUG_<NAME> of include/dfu3d_aug.h is AUG_<NAME> here.
+globals().update({name[len("DFU3D_"):]: value for name, value in _lib_aug.CONSTANTS.items()})
+
+AUG_STATUS_TEXT = {
+    AUG_ST_NONFINITE: "a point's x or y is not finite after the transform",
+    AUG_ST_BOX_CAP: "a scene keeps more boxes than box_cap",
+    AUG_ST_OFFSETS: "point_off / box_off / box_cnt do not describe the arrays",
+}
+
+
+def aug_status_message(word):
+    return "; ".join(t for b, t in AUG_STATUS_TEXT.items() if word & b) or "ok"
+
+
+def aug_params(records):
+    """[{flags, cos_a, sin_a, scale_f, noise_rot_f, tx, ty, tz, noise_rot, scale}, ...] -> uint8 array (B, sizeof
+    dfu3d_aug_params) laid out as the header's struct (missing keys: the neutral value)."""
+    neutral = {"flags": 0, "cos_a": 1.0, "sin_a": 0.0, "scale_f": 1.0, "noise_rot_f": 0.0, "tx": 0.0, "ty": 0.0,
+               "tz": 0.0, "noise_rot": 0.0, "scale": 1.0}
+    arr = (_lib_aug.Params * max(len(records), 1))()
+    for k, r in enumerate(records):
+        unknown = set(r) - set(neutral)
+        if unknown:
+            raise Dfu3dError("aug_params: unknown field(s) %s" % sorted(unknown))
+        for name, dv in neutral.items():
+            setattr(arr[k], name, r.get(name, dv))
+    raw = np.frombuffer(arr, dtype=np.uint8).reshape(max(len(records), 1), ctypes.sizeof(_lib_aug.Params))
+    return raw[:len(records)].copy()
+
+
+def world_aug_collate(points, point_off, boxes, box_off, box_cnt, box_cls, params, pc_range, mode, box_cap, status,
+                      want_aug=False, want_keep=False):
+    """World augmentation, range masks and collate for B scenes (dfu3d_world_aug_collate): points float32 (N, C) by
+    scene (point_off int64 (B+1); N may exceed point_off[B]: the rows behind it are never read); boxes float32 or float64 (Nt, 7|9) with box_off int32 (B+1), box_cnt int32 (B),
+    box_cls int32 (Nt); params uint8 (B, sizeof dfu3d_aug_params) of aug_params(); pc_range float32 (6); mode: AUG_MASK_POINTS |
+    AUG_MASK_BOXES | AUG_FILTER_CLASS -> points_out float32 (N, 1 + C), n_kept int32 (1), point_cnt int32 (B),
+    gt_boxes float32 (B, box_cap, 8|10), gt_cnt int32 (B), boxes_aug (Nt, 7|9) or None, box_keep int32 (Nt) or None.
+    Everything is checked on the host before the first launch; nothing here synchronises or copies to the host."""
+    if not isinstance(points, torch.Tensor) or points.dim() != 2 or points.shape[1] < 3:
+        raise Dfu3dError("world_aug_collate: points must be a (N, C >= 3) tensor")
+    if not isinstance(boxes, torch.Tensor) or boxes.dim() != 2 or boxes.shape[1] not in (7, 9):
+        raise Dfu3dError("world_aug_collate: boxes must be (Nt, 7) or (Nt, 9), got %s"
+                         % (tuple(boxes.shape) if isinstance(boxes, torch.Tensor) else type(boxes),))
+    if boxes.dtype not in (torch.float32, torch.float64):
+        raise Dfu3dError("world_aug_collate: boxes must be float32 or float64, got %s" % boxes.dtype)
+    if not isinstance(box_cnt, torch.Tensor) or box_cnt.dim() != 1:
+        raise Dfu3dError("world_aug_collate: box_cnt must be an int32 tensor (B)")
+    N, C = (int(v) for v in points.shape)
+    nt, nc = (int(v) for v in boxes.shape)
+    B, box_cap, mode = int(box_cnt.shape[0]), int(box_cap), int(mode)
+    if mode & ~(AUG_MASK_POINTS | AUG_MASK_BOXES | AUG_FILTER_CLASS):
+        raise Dfu3dError("world_aug_collate: unknown mode bits in %d" % mode)
+    if N > AUG_MAX_ROWS or B > AUG_MAX_SCENES or C > AUG_MAX_POINT_COLS or box_cap > AUG_MAX_BOX_CAP:
+        raise Dfu3dError("world_aug_collate: N = %d, B = %d, C = %d, box_cap = %d beyond the caps of dfu3d_aug.h "
+                         "(DFU3D_ERANGE)" % (N, B, C, box_cap))
+    if box_cap < 0 or (B == 0 and (N or nt)):
+        raise Dfu3dError("world_aug_collate: box_cap < 0, or rows without a scene")
+    psize = ctypes.sizeof(_lib_aug.Params)
+    dev = points.device
+    pts_p = _chk(points, "points", torch.float32) if N else None
+    box_p = _chk(boxes, "boxes", boxes.dtype) if nt else None
+    cls_p = _chk(box_cls, "box_cls", torch.int32, numel=nt) if nt else None
+    if B:
+        poff_p = _chk(point_off, "point_off", torch.int64, numel=B + 1)
+        boff_p = _chk(box_off, "box_off", torch.int32, numel=B + 1)
+        bcnt_p = _chk(box_cnt, "box_cnt", torch.int32, numel=B)
+        par_p = _chk(params, "params", torch.uint8, numel=B * psize)
+        rng_p = _chk(pc_range, "pc_range", torch.float32, numel=6)
+    else:
+        poff_p = boff_p = bcnt_p = par_p = rng_p = None
+    st_p = _chk(status, "status", torch.int32, numel=1)
+    out = torch.empty((N, C + 1), dtype=torch.float32, device=dev)
+    n_kept = torch.empty(1, dtype=torch.int32, device=dev)
+    point_cnt = torch.empty(B, dtype=torch.int32, device=dev)
+    gt = torch.empty((B, box_cap, nc + 1), dtype=torch.float32, device=dev)
+    gt_cnt = torch.empty(B, dtype=torch.int32, device=dev)
+    aug = torch.empty((nt, nc), dtype=boxes.dtype, device=dev) if want_aug else None
+    keep = torch.empty(nt, dtype=torch.int32, device=dev) if want_keep else None
+    L = _lib_aug.lib()
+    nbytes = int(L.dfu3d_world_aug_scratch_bytes(N))
+    scratch = torch.empty((nbytes + 7) // 8, dtype=torch.int64, device=dev)
+
+    def ptr(t):
+        return ctypes.c_void_p(t.data_ptr()) if t is not None and t.numel() else None
+    rc = L.dfu3d_world_aug_collate(
+        pts_p, N, C, poff_p, B, box_p, 1 if boxes.dtype == torch.float64 else 0, nc, nt, boff_p, bcnt_p, cls_p,
+        ctypes.cast(par_p, ctypes.POINTER(_lib_aug.Params)) if par_p is not None else None, rng_p, mode, ptr(out),
+        ptr(n_kept), ptr(point_cnt), ptr(gt), box_cap, ptr(gt_cnt), ptr(aug), ptr(keep),
+        ctypes.c_void_p(scratch.data_ptr()), nbytes, st_p, _stream())
+    _lib_aug.check(rc, "dfu3d_world_aug_collate")
+    return out, n_kept, point_cnt, gt, gt_cnt, aug, keep
