@@ -1,0 +1,166 @@
+"""pcdet/models/detectors/centerpoint.py (over detector3d_template.py) assembled from this package's modules:
+`vfe` (DynamicPillarVFE) -> `map_to_bev_module` (PointPillarScatter) -> `backbone_2d` (BaseBEVBackbone) -> `dense_head`
+(CenterHeadModule), with the reference's submodule names and its `global_step` buffer, so a reference checkpoint's
+'model_state' loads with strict=True.
+
+`forward(batch_dict)` in training returns ({'loss': loss}, tb_dict, disp_dict) with tb_dict['loss_rpn'] (tb_dict is
+read from the device in one copy); in evaluation (pred_dicts, recall_dict).  Module names of the config this package
+does not have (a BACKBONE_3D, PFE, POINT_HEAD, ROI_HEAD entry, another VFE / MAP_TO_BEV / BACKBONE_2D / DENSE_HEAD name)
+raise NotImplementedError naming them."""
+import os
+
+import torch
+import torch.nn as nn
+
+from . import iou3d_nms_utils
+from .base_bev_backbone import BaseBEVBackbone
+from .center_head_module import CenterHeadModule
+from .dynamic_pillar_vfe import DynamicPillarVFE, DynamicPillarVFESimple2D
+from .pointpillar_scatter import PointPillarScatter, PointPillarScatter3d
+
+
+def _get(cfg, key, *default):
+    if isinstance(cfg, dict):
+        return cfg[key] if not default else cfg.get(key, default[0])
+    return getattr(cfg, key) if not default else getattr(cfg, key, default[0])
+
+
+MODULES = {
+    'VFE': {'DynPillarVFE': DynamicPillarVFE, 'DynamicPillarVFE': DynamicPillarVFE,
+            'DynamicPillarVFESimple2D': DynamicPillarVFESimple2D},
+    'MAP_TO_BEV': {'PointPillarScatter': PointPillarScatter, 'PointPillarScatter3d': PointPillarScatter3d},
+    'BACKBONE_2D': {'BaseBEVBackbone': BaseBEVBackbone},
+    'DENSE_HEAD': {'CenterHead': CenterHeadModule},
+}
+ABSENT = ('BACKBONE_3D', 'PFE', 'POINT_HEAD', 'ROI_HEAD')
+
+
+class _Dataset:
+    def __init__(self, **kw):
+        self.__dict__.update(kw)
+
+
+def _module_class(model_cfg, section):
+    cfg = _get(model_cfg, section, None)
+    if cfg is None:
+        return None, None
+    name = _get(cfg, 'NAME')
+    if name not in MODULES[section]:
+        raise NotImplementedError("CenterPoint: %s.NAME = %r is not part of this package (it has %s)"
+                                  % (section, name, ", ".join(sorted(MODULES[section]))))
+    return cfg, MODULES[section][name]
+
+
+class CenterPoint(nn.Module):
+    def __init__(self, model_cfg, num_class, dataset=None, **kwargs):
+        """dataset: an object with class_names, grid_size, point_cloud_range, voxel_size and
+        point_feature_encoder.num_point_features -- or the same as keywords (num_point_features for the last)."""
+        super().__init__()
+        if dataset is None:
+            feats = kwargs.pop('num_point_features')
+            dataset = _Dataset(point_feature_encoder=_Dataset(num_point_features=feats), **kwargs)
+        self.model_cfg = model_cfg
+        self.num_class = num_class
+        self.dataset = dataset
+        self.class_names = list(dataset.class_names)
+        self.register_buffer('global_step', torch.LongTensor(1).zero_())
+        absent = [s for s in ABSENT if _get(model_cfg, s, None)]
+        if absent:
+            raise NotImplementedError("CenterPoint: the config's %s is not part of this package" % ", ".join(absent))
+        grid_size = [int(v) for v in dataset.grid_size]
+        pc_range = [float(v) for v in dataset.point_cloud_range]
+        voxel_size = [float(v) for v in dataset.voxel_size]
+        self.module_list = []
+        num_bev = None
+        cfg, cls = _module_class(model_cfg, 'VFE')
+        self.vfe = None
+        if cls is not None:
+            self.vfe = cls(model_cfg=cfg, num_point_features=dataset.point_feature_encoder.num_point_features,
+                           point_cloud_range=pc_range, voxel_size=voxel_size, grid_size=grid_size)
+            self.module_list.append(self.vfe)
+        cfg, cls = _module_class(model_cfg, 'MAP_TO_BEV')
+        self.map_to_bev_module = None
+        if cls is not None:
+            self.map_to_bev_module = cls(model_cfg=cfg, grid_size=grid_size)
+            num_bev = self.map_to_bev_module.num_bev_features
+            self.module_list.append(self.map_to_bev_module)
+        cfg, cls = _module_class(model_cfg, 'BACKBONE_2D')
+        self.backbone_2d = None
+        if cls is not None:
+            self.backbone_2d = cls(model_cfg=cfg, input_channels=num_bev)
+            num_bev = self.backbone_2d.num_bev_features
+            self.module_list.append(self.backbone_2d)
+        cfg, cls = _module_class(model_cfg, 'DENSE_HEAD')
+        self.dense_head = None
+        if cls is not None:
+            self.dense_head = cls(
+                model_cfg=cfg, input_channels=num_bev if num_bev is not None else _get(cfg, 'INPUT_FEATURES'),
+                num_class=num_class if not _get(cfg, 'CLASS_AGNOSTIC', False) else 1, class_names=self.class_names,
+                grid_size=grid_size, point_cloud_range=pc_range, voxel_size=voxel_size,
+                predict_boxes_when_training=bool(_get(model_cfg, 'ROI_HEAD', False)))
+            self.module_list.append(self.dense_head)
+
+    @property
+    def mode(self):
+        return 'TRAIN' if self.training else 'TEST'
+
+    def update_global_step(self):
+        self.global_step += 1
+
+    def forward(self, batch_dict):
+        for cur_module in self.module_list:
+            batch_dict = cur_module(batch_dict)
+        if self.training:
+            loss, tb_dict, disp_dict = self.get_training_loss()
+            return {'loss': loss}, tb_dict, disp_dict
+        return self.post_processing(batch_dict)
+
+    def get_training_loss(self):
+        loss_rpn, tb_dict = self.dense_head.get_loss()
+        tb_dict = {'loss_rpn': tb_dict['rpn_loss'], **tb_dict}          # the value get_loss read already: no second copy
+        return loss_rpn, tb_dict, {}
+
+    def post_processing(self, batch_dict):
+        thresh_list = _get(_get(self.model_cfg, 'POST_PROCESSING'), 'RECALL_THRESH_LIST')
+        final_pred_dict = batch_dict['final_box_dicts']
+        recall_dict = {}
+        for index in range(batch_dict['batch_size']):
+            recall_dict = self.generate_recall_record(final_pred_dict[index]['pred_boxes'], recall_dict, index,
+                                                      data_dict=batch_dict, thresh_list=thresh_list)
+        return final_pred_dict, recall_dict
+
+    @staticmethod
+    def generate_recall_record(box_preds, recall_dict, batch_index, data_dict=None, thresh_list=None):
+        """detector3d_template.py generate_recall_record: the ground-truth boxes of a sample (its trailing all-zero rows
+        cut) that some prediction ('rcnn_%s') or roi ('roi_%s') overlaps by more than each threshold, accumulated."""
+        if 'gt_boxes' not in data_dict:
+            return recall_dict
+        rois = data_dict['rois'][batch_index] if 'rois' in data_dict else None
+        gt = data_dict['gt_boxes'][batch_index]
+        if len(recall_dict) == 0:
+            recall_dict = {'gt': 0}
+            for t in thresh_list:
+                recall_dict['roi_%s' % str(t)] = 0
+                recall_dict['rcnn_%s' % str(t)] = 0
+        nonzero = (gt.sum(dim=1) != 0).nonzero()
+        gt = gt[:int(nonzero[-1]) + 1] if len(nonzero) else gt[:0]
+        if gt.shape[0] > 0:
+            iou_rcnn = iou3d_nms_utils.boxes_iou3d_gpu(box_preds[:, 0:7], gt[:, 0:7]) if box_preds.shape[0] > 0 else None
+            iou_roi = iou3d_nms_utils.boxes_iou3d_gpu(rois[:, 0:7], gt[:, 0:7]) if rois is not None else None
+            for t in thresh_list:
+                if iou_rcnn is not None:
+                    recall_dict['rcnn_%s' % str(t)] += int((iou_rcnn.max(dim=0)[0] > t).sum().item())
+                if iou_roi is not None:
+                    recall_dict['roi_%s' % str(t)] += int((iou_roi.max(dim=0)[0] > t).sum().item())
+            recall_dict['gt'] += gt.shape[0]
+        return recall_dict
+
+    def load_params_from_file(self, filename, to_cpu=False, logger=None):
+        """checkpoint['model_state'] into this model, strict: every key and shape must be this model's."""
+        if not os.path.isfile(filename):
+            raise FileNotFoundError(filename)
+        checkpoint = torch.load(filename, map_location=torch.device('cpu') if to_cpu else None)
+        self.load_state_dict(checkpoint['model_state'], strict=True)
+        if logger is not None:
+            logger.info('==> Loaded %d tensors from %s' % (len(checkpoint['model_state']), filename))
+        return checkpoint
