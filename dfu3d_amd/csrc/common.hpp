@@ -126,6 +126,35 @@ __device__ __forceinline__ int block_excl_scan(int v, int *s_w, int &block_total
   return off + inc - v;
 }
 
+// Exclusive prefix of load(0), ..., load(n - 1) by ONE workgroup of NT threads, SI consecutive items per thread and pass:
+// store(i, prefix) for every i < n; returns the total (in every thread).  Tot: type of the prefix and of the carry from
+// pass to pass (one pass must fit an int); Idx: type of n and of i.
+// PRECONDITION (inherited from the DPP scan): ALL threads of the workgroup call it from uniform control flow and NT is
+// a multiple of 64.  s_w: NT / 64 ints of LDS; on return it holds the wave totals of the last pass (nothing new if
+// n <= 0) and every thread is past the last barrier, so it is reusable at once.
+template <int NT, int SI, class Tot, class Idx, class Load, class Store>
+__device__ __forceinline__ Tot block_scan_range(Idx n, Load load, Store store, int *s_w) {
+  Tot carry = 0;
+  for (Idx base = 0; base < n; base += NT * SI) {
+    const Idx i0 = base + (Idx)threadIdx.x * SI;
+    int v[SI], sum = 0;
+#pragma unroll
+    for (int k = 0; k < SI; k++) {
+      v[k] = i0 + k < n ? load(i0 + k) : 0;
+      sum += v[k];
+    }
+    int tot;
+    Tot ex = block_excl_scan<NT / 64>(sum, s_w, tot) + carry;
+#pragma unroll
+    for (int k = 0; k < SI; k++) {
+      if (i0 + k < n) store(i0 + k, ex);
+      ex += v[k];
+    }
+    carry += tot;
+  }
+  return carry;
+}
+
 // ---- fp64 wave reductions ---------------------------------------------------
 __device__ __forceinline__ double shfl_xor_d(double v, int m) {
   int lo = __double2loint(v), hi = __double2hiint(v);
@@ -190,6 +219,19 @@ __device__ __forceinline__ unsigned long long wave_sum_u64(unsigned long long v)
   return v;
 }
 __device__ __forceinline__ int wave_sum_i(int v) { return wave_sum_i_dpp(v); }
+// Sum of an int over a workgroup of NW waves with ONE barrier; the result in every thread that reads it (same
+// precondition as wave_sum_i, all waves).  s_w: NW ints of LDS, read AFTER the barrier: not reusable until the caller
+// has passed a barrier of its own.
+template <int NW>
+__device__ __forceinline__ int block_sum_i(int v, int *s_w) {
+  v = wave_sum_i(v);
+  if (lane_id() == 0) s_w[threadIdx.x >> 6] = v;
+  __syncthreads();
+  int t = 0;
+#pragma unroll
+  for (int w = 0; w < NW; w++) t += s_w[w];
+  return t;
+}
 
 // ---- calibration arithmetic -------------------------------------------------
 // calibration_kitti.py:104-112, float32: sequential-k FMA chain (== sgemm).

@@ -45,32 +45,19 @@ __global__ __launch_bounds__(GT) void k_pib_count(const float4 *__restrict__ pts
     const float4 p = pts[p0 + i];
     c += pt_in_box(q, p.x, p.y, p.z) ? 1 : 0;
   }
-  c = wave_sum_i(c);
-  if (lane_id() == 0) s_w[threadIdx.x >> 6] = c;
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    int t = 0;
-    for (int w = 0; w < GT / 64; w++) t += s_w[w];
-    cnt[b] = t;
-  }
+  c = block_sum_i<GT / 64>(c, s_w);
+  if (threadIdx.x == 0) cnt[b] = c;
 }
 
 __global__ __launch_bounds__(1024) void k_pib_scan(int B, const int *__restrict__ cnt,
                                                    long long *__restrict__ off, long long cap,
                                                    uint32_t *__restrict__ status) {
   __shared__ int s_w[16];
-  long long running = 0;
-  for (int b0 = 0; b0 < B; b0 += 1024) {
-    const int b = b0 + threadIdx.x;
-    const int v = (b < B) ? cnt[b] : 0;
-    int tot;
-    const int ex = block_excl_scan<16>(v, s_w, tot);
-    if (b < B) off[b] = running + ex;
-    running += tot;
-  }
+  const long long total = block_scan_range<1024, 1, long long, int>(
+      B, [&](int b) { return cnt[b]; }, [&](int b, long long ex) { off[b] = ex; }, s_w);
   if (threadIdx.x == 0) {
-    off[B] = running;
-    if (running > cap) atomicOr(status, DFU3D_ST_POOL_OVERFLOW);
+    off[B] = total;
+    if (total > cap) atomicOr(status, DFU3D_ST_POOL_OVERFLOW);
   }
 }
 

@@ -157,10 +157,8 @@ __global__ __launch_bounds__(PT) void k_gts_count(const float *__restrict__ pts,
   if (slot == 0) {
     int c = 0;
     for (int a = threadIdx.x; a < na; a += PT) c += obj_cnt[s_row[a]];
-    c = wave_sum_i(c);
-    if (lane_id() == 0) s_w[threadIdx.x >> 6] = c;
-    __syncthreads();
-    if (threadIdx.x == 0) cnt[(size_t)b * S] = s_w[0] + s_w[1] + s_w[2] + s_w[3];
+    c = block_sum_i<PT / 64>(c, s_w);
+    if (threadIdx.x == 0) cnt[(size_t)b * S] = c;
     return;
   }
   for (int a = threadIdx.x; a < na; a += PT) s_box[a] = load_box(large + (size_t)s_row[a] * 7);
@@ -177,10 +175,8 @@ __global__ __launch_bounds__(PT) void k_gts_count(const float *__restrict__ pts,
       mine += in ? 0 : 1;
     }
   }
-  mine = wave_sum_i(mine);
-  if (lane_id() == 0) s_w[threadIdx.x >> 6] = mine;
-  __syncthreads();
-  if (threadIdx.x == 0) cnt[(size_t)b * S + slot] = s_w[0] + s_w[1] + s_w[2] + s_w[3];
+  mine = block_sum_i<PT / 64>(mine, s_w);
+  if (threadIdx.x == 0) cnt[(size_t)b * S + slot] = mine;
 }
 
 // exclusive scan of the B * S slot counts -> slot_off (int64); out_off[b] = slot_off[b * S], out_off[B] = total
@@ -188,22 +184,16 @@ __global__ __launch_bounds__(1024) void k_gts_scan(int B, int S, const int *__re
                                                    long long *__restrict__ slot_off, long long *__restrict__ out_off,
                                                    long long cap, uint32_t *__restrict__ status) {
   __shared__ int s_w[16];
-  const long long total_slots = (long long)B * S;
-  long long running = 0;
-  for (long long s0 = 0; s0 < total_slots; s0 += 1024) {
-    const long long s = s0 + threadIdx.x;
-    const int v = (s < total_slots) ? cnt[s] : 0;
-    int tot;
-    const int ex = block_excl_scan<16>(v, s_w, tot);
-    if (s < total_slots) {
-      slot_off[s] = running + ex;
-      if (s % S == 0) out_off[s / S] = running + ex;
-    }
-    running += tot;
-  }
+  const long long total = block_scan_range<1024, 1, long long, long long>(
+      (long long)B * S, [&](long long s) { return cnt[s]; },
+      [&](long long s, long long ex) {
+        slot_off[s] = ex;
+        if (s % S == 0) out_off[s / S] = ex;
+      },
+      s_w);
   if (threadIdx.x == 0) {
-    out_off[B] = running;
-    if (running > cap) atomicOr(status, DFU3D_ST_POOL_OVERFLOW);
+    out_off[B] = total;
+    if (total > cap) atomicOr(status, DFU3D_ST_POOL_OVERFLOW);
   }
 }
 

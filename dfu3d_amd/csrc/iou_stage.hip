@@ -70,16 +70,8 @@ __global__ __launch_bounds__(IB) void k_suppress_mask(const float *__restrict__ 
   bool over = false;
   if (j < n && j > i) {
     const Rect A = make_rect(boxes + (size_t)i * 7, 7), B = make_rect(boxes + (size_t)j * 7, 7);
-    float inter;
-    if (normal) {                                           // headings ignored
-      const float w = fminf(A.cx + A.hu, B.cx + B.hu) - fmaxf(A.cx - A.hu, B.cx - B.hu);
-      const float h = fminf(A.cy + A.hv, B.cy + B.hv) - fmaxf(A.cy - A.hv, B.cy - B.hv);
-      inter = fmaxf(w, 0.0f) * fmaxf(h, 0.0f);
-    } else {
-      inter = overlap_area(A, B, s_poly[0] + threadIdx.x, s_poly[1] + threadIdx.x, s_poly[2] + threadIdx.x,
-                           s_poly[3] + threadIdx.x);
-    }
-    over = criterion_value(inter, A, B, 1) > thresh;
+    over = nms_suppresses(A, B, normal, thresh, s_poly[0] + threadIdx.x, s_poly[1] + threadIdx.x, s_poly[2] + threadIdx.x,
+                          s_poly[3] + threadIdx.x);
   }
   const unsigned long long word = __ballot(over);
   if (lane == 0) mask[(size_t)i * nblk + cb] = word;

@@ -97,36 +97,18 @@ __global__ __launch_bounds__(PT) void k_pv_mark(const float *__restrict__ pts, i
   if (threadIdx.x == 0) blk_cnt[blockIdx.x] = tot;
 }
 
-// exclusive prefix of load(0..n) into out, by one workgroup of ST threads; returns the total (in every thread)
+// exclusive prefix of load(0..n) into out by the one workgroup of ST threads; returns the total (in every thread)
 template <class F>
-__device__ __forceinline__ int scan_one_block(int n, F load, int *__restrict__ out, int *s_w) {
-  int carry = 0;
-  for (int base = 0; base < n; base += ST * SI) {
-    const int i0 = base + (int)threadIdx.x * SI;
-    int v[SI], sum = 0;
-#pragma unroll
-    for (int k = 0; k < SI; k++) {
-      v[k] = i0 + k < n ? load(i0 + k) : 0;
-      sum += v[k];
-    }
-    int tot;
-    int ex = block_excl_scan<ST / 64>(sum, s_w, tot) + carry;
-#pragma unroll
-    for (int k = 0; k < SI; k++) {
-      if (i0 + k < n) out[i0 + k] = ex;
-      ex += v[k];
-    }
-    carry += tot;
-  }
-  return carry;
+__device__ __forceinline__ int pv_scan(int n, F load, int *__restrict__ out, int *s_w) {
+  return block_scan_range<ST, SI, int, int>(n, load, [&](int i, int ex) { out[i] = ex; }, s_w);
 }
 
 __global__ __launch_bounds__(ST) void k_pv_scan(const uint32_t *__restrict__ bitmap, int words, int *__restrict__ wpre,
                                                 const int *__restrict__ blk_cnt, int blocks, int *__restrict__ blk_off,
                                                 int *__restrict__ sizes) {
   __shared__ int s_w[ST / 64];
-  const int P = scan_one_block(words, [&](int i) { return __popc(bitmap[i]); }, wpre, s_w);
-  const int kept = scan_one_block(blocks, [&](int i) { return blk_cnt[i]; }, blk_off, s_w);
+  const int P = pv_scan(words, [&](int i) { return __popc(bitmap[i]); }, wpre, s_w);
+  const int kept = pv_scan(blocks, [&](int i) { return blk_cnt[i]; }, blk_off, s_w);
   if (threadIdx.x == 0) {
     sizes[0] = kept;
     sizes[1] = P;
@@ -165,7 +147,7 @@ __global__ __launch_bounds__(ST) void k_pv_offsets(const int *__restrict__ cnt, 
                                                    int *__restrict__ offsets) {
   __shared__ int s_w[ST / 64];
   const int P = sizes[1];
-  const int tot = scan_one_block(P, [&](int i) { return cnt[i]; }, offsets, s_w);
+  const int tot = pv_scan(P, [&](int i) { return cnt[i]; }, offsets, s_w);
   if (threadIdx.x == 0) offsets[P] = tot;
 }
 

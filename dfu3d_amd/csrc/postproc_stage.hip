@@ -9,7 +9,7 @@
 //
 //   k_pp_mask     one wave per row i of a segment: the wave goes over the 64-box blocks from i's own to the segment's last;
 //                 lane l tests box 64 cb + l against box i and the ballot is the word, as in k_suppress_mask
-//                 (iou_stage.hip), with the same expressions in the same roles -- a pair's decision is the same bits.
+//                 (iou_stage.hip); both decide a pair with nms_suppresses (rect_overlap.hpp): the same bits.
 //   k_pp_walk     one workgroup per segment.  The mask rows are staged in LDS where they fit (up to 704 rows; 500 rows x 8 words
 //                 = 32 KB), then wave 0 walks 64 rows at a time: lane l holds the diagonal word of row 64 blk + l, the
 //                 greedy chain inside the block runs on wave-uniform values (a find-first-zero and a lane read per KEPT
@@ -65,16 +65,8 @@ __global__ __launch_bounds__(IB) void k_pp_mask(const float *__restrict__ boxes,
     bool over = false;
     if (j < n && j > i) {
       const Rect B = make_rect(seg + (size_t)j * C, 7);
-      float inter;
-      if (normal) {                                          // headings ignored
-        const float w = fminf(A.cx + A.hu, B.cx + B.hu) - fmaxf(A.cx - A.hu, B.cx - B.hu);
-        const float h = fminf(A.cy + A.hv, B.cy + B.hv) - fmaxf(A.cy - A.hv, B.cy - B.hv);
-        inter = fmaxf(w, 0.0f) * fmaxf(h, 0.0f);
-      } else {
-        inter = overlap_area(A, B, s_poly[0] + threadIdx.x, s_poly[1] + threadIdx.x, s_poly[2] + threadIdx.x,
-                             s_poly[3] + threadIdx.x);
-      }
-      over = criterion_value(inter, A, B, 1) > thresh;
+      over = nms_suppresses(A, B, normal, thresh, s_poly[0] + threadIdx.x, s_poly[1] + threadIdx.x,
+                            s_poly[2] + threadIdx.x, s_poly[3] + threadIdx.x);
     }
     const unsigned long long word = __ballot(over);
     if (lane == 0) row[cb] = word;

@@ -103,4 +103,20 @@ __device__ __forceinline__ float criterion_value(float inter, const Rect &A, con
   return inter / fmaxf(crit == 2 ? sa : sb, 1e-8f);
 }
 
+// The decision of one pair of an NMS, the ONE definition for k_suppress_mask (iou_stage.hip) and k_pp_mask
+// (postproc_stage.hip): does A suppress B?  normal != 0: axis-aligned IoU, headings ignored (the reference's
+// nms_normal).  pu .. qv as in overlap_area.
+__device__ __forceinline__ bool nms_suppresses(const Rect &A, const Rect &B, int normal, float thresh, float *pu,
+                                               float *pv, float *qu, float *qv) {
+  float inter;
+  if (normal) {
+    const float w = fminf(A.cx + A.hu, B.cx + B.hu) - fmaxf(A.cx - A.hu, B.cx - B.hu);
+    const float h = fminf(A.cy + A.hv, B.cy + B.hv) - fmaxf(A.cy - A.hv, B.cy - B.hv);
+    inter = fmaxf(w, 0.0f) * fmaxf(h, 0.0f);
+  } else {
+    inter = overlap_area(A, B, pu, pv, qu, qv);
+  }
+  return criterion_value(inter, A, B, 1) > thresh;
+}
+
 }  // namespace

@@ -251,19 +251,18 @@ __global__ __launch_bounds__(SEG_WPB * 64) void k_seg_write(
 }
 
 // ---------------------------------------------------------------- tiles
+// tile_off[s] = tiles of the segments before s, tile_off[S] = all tiles; tiles(s): tiles of segment s.  One workgroup
+// of 1024 threads.
+template <class F>
+__device__ __forceinline__ void tile_scan(int S, F tiles, int *__restrict__ tile_off) {
+  __shared__ int s_w[16];
+  const int total = block_scan_range<1024, 1, int, int>(S, tiles, [&](int s, int ex) { tile_off[s] = ex; }, s_w);
+  if (threadIdx.x == 0) tile_off[S] = total;
+}
+
 __global__ __launch_bounds__(1024) void k_tile_scan(int S, const int *__restrict__ cnt,
                                                     int *__restrict__ tile_off, int qt) {
-  __shared__ int s_w[16];
-  int running = 0;
-  for (int b0 = 0; b0 < S; b0 += 1024) {
-    const int s = b0 + threadIdx.x;
-    const int nt = (s < S) ? (cnt[s] + qt - 1) / qt : 0;
-    int tot;
-    const int ex = block_excl_scan<16>(nt, s_w, tot);
-    if (s < S) tile_off[s] = running + ex;
-    running += tot;
-  }
-  if (threadIdx.x == 0) tile_off[S] = running;
+  tile_scan(S, [&](int s) { return (cnt[s] + qt - 1) / qt; }, tile_off);
 }
 
 // largest s with tile_off[s] <= t  (t < tile_off[S])
@@ -1036,21 +1035,10 @@ constexpr int BT_SMALL = 256, BH_HEADS_SMALL = 2048, BH_MAX_SMALL = 1024; // 8 K
 // query tiles of the segments whose LiDAR list has lo < cnt_a <= hi entries
 __global__ __launch_bounds__(1024) void k_tile_scan_class(int S, const int *__restrict__ cnt, const int *__restrict__ cnt_a,
                                                           int lo, int hi, int *__restrict__ tile_off, int qt) {
-  __shared__ int s_w[16];
-  int running = 0;
-  for (int b0 = 0; b0 < S; b0 += 1024) {
-    const int s = b0 + threadIdx.x;
-    int nt = 0;
-    if (s < S) {
-      const int na = cnt_a[s];
-      if (na > lo && na <= hi) nt = (cnt[s] + qt - 1) / qt;
-    }
-    int tot;
-    const int ex = block_excl_scan<16>(nt, s_w, tot);
-    if (s < S) tile_off[s] = running + ex;
-    running += tot;
-  }
-  if (threadIdx.x == 0) tile_off[S] = running;
+  tile_scan(S, [&](int s) {
+    const int na = cnt_a[s];
+    return (na > lo && na <= hi) ? (cnt[s] + qt - 1) / qt : 0;
+  }, tile_off);
 }
 
 // |a - b| in one instruction (the compiler expands __sad() into subtract, negate, max)

@@ -242,25 +242,16 @@ __global__ __launch_bounds__(PT) void k_wa_count(const float *__restrict__ pts, 
   int s_lo, s_hi;
   int mine = rows_of<false>(pts, n_rows, C, point_off, B, params, range, mode, blockIdx.x, R, nonfinite, s_lo, s_hi);
   if (nonfinite) atomicOr(status, (uint32_t)DFU3D_AUG_ST_NONFINITE);
-  mine = wave_sum_i(mine);
-  if (lane_id() == 0) s_w[threadIdx.x >> 6] = mine;
-  __syncthreads();
-  if (threadIdx.x == 0) cnt[blockIdx.x] = s_w[0] + s_w[1] + s_w[2] + s_w[3];
+  mine = block_sum_i<PT / 64>(mine, s_w);
+  if (threadIdx.x == 0) cnt[blockIdx.x] = mine;
 }
 
 __global__ __launch_bounds__(1024) void k_wa_scan(int n_chunks, const int *__restrict__ cnt, int *__restrict__ off,
                                                   int *__restrict__ n_kept) {
   __shared__ int s_w[16];
-  int running = 0;
-  for (int c0 = 0; c0 < n_chunks; c0 += 1024) {
-    const int c = c0 + threadIdx.x;
-    const int v = (c < n_chunks) ? cnt[c] : 0;
-    int tot;
-    const int ex = block_excl_scan<16>(v, s_w, tot);
-    if (c < n_chunks) off[c] = running + ex;
-    running += tot;
-  }
-  if (threadIdx.x == 0) n_kept[0] = running;
+  const int total = block_scan_range<1024, 1, int, int>(
+      n_chunks, [&](int c) { return cnt[c]; }, [&](int c, int ex) { off[c] = ex; }, s_w);
+  if (threadIdx.x == 0) n_kept[0] = total;
 }
 
 __global__ __launch_bounds__(PT) void k_wa_write(const float *__restrict__ pts, long long n_rows, int C,

@@ -221,3 +221,38 @@ def test_edge_cases_and_determinism(tmp_path):
     assert len(scenes[17]["points"]) == 0 and len(outs[0][1][17]["points"]) > 0      # 0 scene points + pasted objects
     assert np.array_equal(outs[0][1][13]["gt_names"], np.array(['Van']))
     assert np.array_equal(outs[0][1][11]["points"], scenes[11]["points"])
+
+
+def test_more_slots_than_one_pass_of_the_offset_scan(tmp_path):
+    """350 scenes of at most 2048 points are 350 x 3 slots (the pasted objects + two chunks of 1024 points): the one
+    workgroup that scans the slot counts 1024 at a time carries its running total into a second pass, and the scenes
+    from 342 on take their offsets from it."""
+    from dfu3d_amd.pcdet_kitti.database_sampler import DataBaseSampler
+    rng = np.random.default_rng(23)
+    boxes = [[rng.uniform(-40, 40), rng.uniform(-40, 40), -1.0, 4.0, 1.8, 1.5, rng.uniform(-3, 3)] for _ in range(40)]
+    _planted_db(tmp_path, boxes, [['Car', 'Pedestrian'][k % 2] for k in range(40)], npts=30)
+    cfg = _cfg(['Car:3', 'Pedestrian:2'], width=(0.2, 0.2, 0.0))
+    scenes = []
+    for s in range(350):
+        n = 2048 if s == 7 else int(rng.integers(40, 2049))
+        p = np.zeros((n, 4), np.float32)
+        p[:, :2] = rng.uniform(-45, 45, (n, 2))
+        p[:, 2] = rng.uniform(-2, 0, n)
+        p[:, 3] = rng.random(n)
+        scenes.append({'points': p, 'gt_boxes': np.zeros((0, 7), np.float32), 'gt_names': np.array([], '<U10'),
+                       'gt_boxes_mask': np.ones(0, bool)})
+    slots = 1 + (max(len(d['points']) for d in scenes) + 1023) // 1024                 # per scene, as the stage cuts them
+    assert slots == 3 and len(scenes) * slots > 1024                                   # what the test is for
+    first_behind = -(-1024 // slots)                                                   # first scene whose slots all lie in pass two
+    copy = lambda: [{k: v.copy() for k, v in d.items()} for d in scenes]
+    ref = R.RefSampler(tmp_path, cfg, ['Car', 'Pedestrian'])
+    np.random.seed(4)
+    exp = [ref(d)[0] for d in copy()]
+    smp = DataBaseSampler(tmp_path, cfg, ['Car', 'Pedestrian'], device=DEV)
+    np.random.seed(4)
+    got = smp.sample_batch(copy()).split()
+    for s in range(len(scenes)):
+        _same(got[s], exp[s]["points"], exp[s]["gt_boxes"], exp[s]["gt_names"], s)
+    behind = range(first_behind, len(scenes))
+    assert any(len(got[s]["gt_names"]) > 0 for s in behind)                            # objects are pasted there
+    assert any(len(got[s]["points"]) > 30 * len(got[s]["gt_names"]) for s in behind)   # and scene points are kept

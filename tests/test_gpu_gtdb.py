@@ -12,7 +12,7 @@ pytestmark = pytest.mark.gpu
 DEV = "cuda:0"
 
 
-def _scene(rng, n, nb):
+def _scene(rng, n, nb, size=(0.4, 12.0)):
     pts = np.zeros((n, 4), np.float32)
     pts[:, :2] = rng.uniform(-40, 40, (n, 2))
     pts[:, 2] = rng.uniform(-2.5, 1.5, n)
@@ -20,7 +20,7 @@ def _scene(rng, n, nb):
     boxes = np.zeros((nb, 7))
     boxes[:, :2] = rng.uniform(-35, 35, (nb, 2))
     boxes[:, 2] = rng.uniform(-1.5, 0.0, nb)
-    boxes[:, 3:6] = rng.uniform(0.4, 12.0, (nb, 3))
+    boxes[:, 3:6] = rng.uniform(size[0], size[1], (nb, 3))
     boxes[:, 6] = rng.uniform(-4, 4, nb)
     # points planted on faces / inside the margin band of the first boxes
     for b in range(min(nb, 4) if n >= 64 else 0):
@@ -47,10 +47,10 @@ def test_points_in_boxes_mask_matches_oracle():
             assert exp.sum() > 0
 
 
-def test_gt_database_many_frames_matches_oracle():
+def _database_matches_oracle(frames):
+    """One gt_database call over the frames [(points, boxes), ...]: counts, offsets, indices and points of every box
+    against the oracle, bit exact.  -> (device operands, counts)."""
     from dfu3d_amd import stages as st
-    rng = np.random.default_rng(6)
-    frames = [_scene(rng, n, nb) for n, nb in ((3000, 9), (1, 2), (20000, 31), (500, 0), (8000, 5))]
     off = np.zeros(len(frames) + 1, np.int64)
     off[1:] = np.cumsum([f[0].shape[0] for f in frames])
     pts = torch.from_numpy(np.concatenate([f[0] for f in frames])).to(DEV)
@@ -72,10 +72,32 @@ def test_gt_database_many_frames_matches_oracle():
             exp_pts = G.gt_points_of_box(p, b[i], ind[i])
             assert np.array_equal(gt[boff[k]:boff[k + 1]].view(np.uint32), exp_pts.view(np.uint32))   # bit exact
             k += 1
+    assert boff[0] == 0 and k == len(cnt)
+    return (pts, off, bf, boxes), cnt
+
+
+def test_gt_database_many_frames_matches_oracle():
+    from dfu3d_amd import stages as st
+    rng = np.random.default_rng(6)
+    frames = [_scene(rng, n, nb) for n, nb in ((3000, 9), (1, 2), (20000, 31), (500, 0), (8000, 5))]
+    (pts, off, bf, boxes), cnt = _database_matches_oracle(frames)
     # capacity overflow is flagged, counts stay exact
     c2, _, _, _, s2 = st.gt_database(pts, torch.from_numpy(off.astype(np.int32)).to(DEV), torch.from_numpy(bf).to(DEV),
                                      torch.from_numpy(boxes).to(DEV), 8, host_pt_off=off)
     assert int(s2.item()) & st.ST_POOL_OVERFLOW and np.array_equal(c2.cpu().numpy(), cnt)
+
+
+def test_gt_database_more_boxes_than_one_pass_of_the_offset_scan():
+    """2 300 small boxes over four frames of a few hundred points in ONE call: the offsets come from one workgroup that
+    scans the box counts 1024 at a time, so its running total crosses two pass boundaries.  Most boxes are empty; some
+    behind each boundary are not."""
+    rng = np.random.default_rng(16)
+    frames = [_scene(rng, n, nb, size=(0.5, 2.5)) for n, nb in ((400, 700), (300, 500), (500, 600), (350, 500))]
+    _, cnt = _database_matches_oracle(frames)
+    assert len(cnt) > 2048                                             # what the test is for: more than two passes
+    full = np.nonzero(cnt)[0]
+    assert (full < 1024).any() and ((full >= 1024) & (full < 2048)).any() and (full >= 2048).any()
+    assert 8 * len(full) < len(cnt)
 
 
 def test_create_groundtruth_database_from_pseudo_labels(tmp_path):

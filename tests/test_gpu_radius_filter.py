@@ -25,31 +25,9 @@ def _t(a):
     return torch.as_tensor(np.ascontiguousarray(a)).to(DEV).contiguous()
 
 
-def test_joint_filter_then_joint_fuse_equals_filter_filter_fuse(st):
-    """ONE radius-filter pass over the 2S lists (A = LiDAR, B = pseudo; no compaction) + dfu3d_ballquery_fuse_joint
-    == remove_radius_outlier(A), remove_radius_outlier(B), BallQuery, cat -- including instances whose LiDAR list the
-    filter empties (isolated points, or radius -1: hazard H4), where the fuse is skipped and every filtered pseudo point
-    stays (my_loader.py:602), LiDAR lists beyond both hash-table builds (brute-force tiles) and empty lists."""
-    rng = np.random.default_rng(2024)
-    #        na    nb   r_a   r_b
-    cases = [(0, 40, 3.0, 0.6), (30, 0, 3.0, 3.0), (60, 700, 3.0, 0.6), (900, 4000, 3.0, 3.0), (5, 5, 0.6, 0.6),
-             (4200, 3000, 3.0, 3.0), (7, 300, 3.0, 0.6), (12, 500, -1.0, 0.6), (1500, 2500, 0.6, 0.6), (300, 600, 0.0, 3.0)]
-    segsA, segsB = [], []
-    for k, (na, nb, ra, rb) in enumerate(cases):
-        a = rng.normal(0, 2.0, (na, 3))
-        b = rng.normal(0, 2.0, (nb, 3))
-        if na and nb:
-            h = nb // 2
-            b[:h] = a[rng.integers(0, na, h)] + rng.normal(0, 0.06, (h, 3))
-            far = rng.random(nb) < 0.2                              # isolated pseudo points: the filter drops them
-            b[far] = rng.uniform(-300, 300, (int(far.sum()), 3))
-            fa = rng.random(na) < 0.15                              # and isolated LiDAR points
-            a[fa] = rng.uniform(-300, 300, (int(fa.sum()), 3)) + 1000.0
-        if k == 6:                                                  # every LiDAR point isolated: the filter empties the list
-            a = rng.uniform(-1, 1, (na, 3)) + np.arange(na)[:, None] * 50.0 + 2000.0
-        segsA.append(a)
-        segsB.append(b)
-    S = len(cases)
+def _joint_filter_then_fuse_equals_oracle(st, segsA, segsB, ra, rb):
+    """-> the number of instances whose fuse was skipped because the filter emptied a list"""
+    S = len(segsA)
     chunks, base_a, base_b, cur = [], [], [], 0
     for a, b in zip(segsA, segsB):
         base_a.append(cur); cur += len(a)
@@ -62,7 +40,6 @@ def test_joint_filter_then_joint_fuse_equals_filter_filter_fuse(st):
     cnt_a = _t(np.array([len(a) for a in segsA], np.int32))
     cnt_b = _t(np.array([len(b) for b in segsB], np.int32))
     ta, tb = _t(np.array(base_a, np.int64)), _t(np.array(base_b, np.int64))
-    ra = np.array([c[2] for c in cases]); rb = np.array([c[3] for c in cases])
     # the joint table, as dfu3d_segments_build lays it out: s < S the A lists, S + s the B lists
     base_ab = torch.cat([ta, tb]); cnt_ab = torch.cat([cnt_a, cnt_b]); rad_ab = _t(np.concatenate([ra, rb]))
     tile_off = torch.zeros(2 * S + 2, dtype=torch.int32, device=DEV)
@@ -95,7 +72,95 @@ def test_joint_filter_then_joint_fuse_equals_filter_filter_fuse(st):
         assert ncb[s] == int(keep.sum()), (s, ncb[s], int(keep.sum()))
         assert nbb[s] == base_a[s] + len(a1), s
         assert np.array_equal(X[base_a[s]:base_a[s] + len(exp)], exp), s
+    return skipped
+
+
+def test_joint_filter_then_joint_fuse_equals_filter_filter_fuse(st):
+    """ONE radius-filter pass over the 2S lists (A = LiDAR, B = pseudo; no compaction) + dfu3d_ballquery_fuse_joint
+    == remove_radius_outlier(A), remove_radius_outlier(B), BallQuery, cat -- including instances whose LiDAR list the
+    filter empties (isolated points, or radius -1: hazard H4), where the fuse is skipped and every filtered pseudo point
+    stays (my_loader.py:602), LiDAR lists beyond both hash-table builds (brute-force tiles) and empty lists."""
+    rng = np.random.default_rng(2024)
+    #        na    nb   r_a   r_b
+    cases = [(0, 40, 3.0, 0.6), (30, 0, 3.0, 3.0), (60, 700, 3.0, 0.6), (900, 4000, 3.0, 3.0), (5, 5, 0.6, 0.6),
+             (4200, 3000, 3.0, 3.0), (7, 300, 3.0, 0.6), (12, 500, -1.0, 0.6), (1500, 2500, 0.6, 0.6), (300, 600, 0.0, 3.0)]
+    segsA, segsB = [], []
+    for k, (na, nb, ra, rb) in enumerate(cases):
+        a = rng.normal(0, 2.0, (na, 3))
+        b = rng.normal(0, 2.0, (nb, 3))
+        if na and nb:
+            h = nb // 2
+            b[:h] = a[rng.integers(0, na, h)] + rng.normal(0, 0.06, (h, 3))
+            far = rng.random(nb) < 0.2                              # isolated pseudo points: the filter drops them
+            b[far] = rng.uniform(-300, 300, (int(far.sum()), 3))
+            fa = rng.random(na) < 0.15                              # and isolated LiDAR points
+            a[fa] = rng.uniform(-300, 300, (int(fa.sum()), 3)) + 1000.0
+        if k == 6:                                                  # every LiDAR point isolated: the filter empties the list
+            a = rng.uniform(-1, 1, (na, 3)) + np.arange(na)[:, None] * 50.0 + 2000.0
+        segsA.append(a)
+        segsB.append(b)
+    ra = np.array([c[2] for c in cases]); rb = np.array([c[3] for c in cases])
+    skipped = _joint_filter_then_fuse_equals_oracle(st, segsA, segsB, ra, rb)
     assert skipped >= 2                      # the emptied-list cases were really there
+
+
+def test_more_segments_than_one_pass_of_the_tile_scans(st):
+    """1100 instances with a LiDAR and a pseudo list of 0 to 40 points each, several of them empty.  Every scan over the
+    segments is one workgroup that takes 1024 of them per pass, so its running total is carried into a second and a
+    third pass: k_tile_scan over the 2200 joint lists (radius filter) and over the 1100 pseudo lists (statistical
+    filter), k_tile_scan_class over the instances (fuse).  The voxel down-sample (a workgroup per segment) runs over the
+    same lists."""
+    rng = np.random.default_rng(77)
+    S = 1100
+    segsA, segsB = [], []
+    for s in range(S):
+        na, nb = (0 if s % 9 == 4 else int(rng.integers(1, 41))), (0 if s % 13 == 6 else int(rng.integers(1, 41)))
+        c = rng.uniform(-30, 30, 3)
+        a = np.cumsum(rng.normal(0, 0.02, (na, 3)), 0) + c                 # a surface-like run: a few points per 5 cm voxel
+        b = np.cumsum(rng.normal(0, 0.02, (nb, 3)), 0) + c
+        if na and nb:
+            b[:nb // 2] = a[rng.integers(0, na, nb // 2)] + rng.normal(0, 0.06, (nb // 2, 3))
+            far = rng.random(nb) < 0.2                                      # isolated points: the filter drops them
+            b[far] = rng.uniform(-300, 300, (int(far.sum()), 3)) + 1000.0
+            fa = rng.random(na) < 0.15
+            a[fa] = rng.uniform(-300, 300, (int(fa.sum()), 3)) + 3000.0
+        segsA.append(a)
+        segsB.append(b)
+    lens = np.array([len(b) for b in segsB])
+    assert S > 1024 and (lens[1024:] > 0).sum() > 50 and (lens == 0).sum() > 50        # what the test is for
+    assert (np.array([len(a) for a in segsA]) == 0).sum() > 50
+    ra = np.where(np.arange(S) % 2, 3.0, 0.6)
+    rb = np.where(np.arange(S) % 3, 0.6, 3.0)
+    _joint_filter_then_fuse_equals_oracle(st, segsA, segsB, ra, rb)
+
+    # the pseudo lists alone: voxel down-sample, and the statistical filter
+    base, cur, chunks = [], 0, []
+    for b in segsB:
+        base.append(cur); chunks.append(b); cur += len(b)
+    cap = cur + 8
+    Pp = np.full((cap, 3), 555.0); Pp[:cur] = np.concatenate(chunks)
+    enable = _t(np.ones(S, np.int32))
+    px, py, pz = _t(Pp[:, 0]), _t(Pp[:, 1]), _t(Pp[:, 2])
+    cnt = _t(lens.astype(np.int32))
+    status = torch.zeros(1, dtype=torch.int32, device=DEV)
+    scratch = torch.empty(st.voxel_down_sample_scratch_bytes(cap), dtype=torch.uint8, device=DEV)
+    st.voxel_down_sample(px, py, pz, _t(np.array(base, np.int64)), cnt, enable, 0.05, S, cap, scratch, status)
+    X, n_out = torch.stack([px, py, pz], 1).cpu().numpy(), cnt.cpu().numpy()
+    assert int(status.item()) == 0
+    for s, b in enumerate(segsB):
+        exp = O.voxel_down_sample(b, 0.05)
+        assert n_out[s] == len(exp), (s, n_out[s], len(exp))
+        assert np.array_equal(X[base[s]:base[s] + len(exp)], exp), s
+    px, py, pz = _t(Pp[:, 0]), _t(Pp[:, 1]), _t(Pp[:, 2])
+    cnt = _t(lens.astype(np.int32))
+    st.stat_filter(px, py, pz, _t(np.array(base, np.int64)), cnt, enable, 5, 0.3, S, cap,
+                   torch.zeros(S + 1, dtype=torch.int32, device=DEV), torch.zeros(cap, dtype=torch.uint8, device=DEV),
+                   torch.zeros(cap, dtype=torch.float64, device=DEV))
+    X, n_out = torch.stack([px, py, pz], 1).cpu().numpy(), cnt.cpu().numpy()
+    for s, b in enumerate(segsB):
+        keep = O.statistical_outlier(b, 5, 0.3)
+        assert n_out[s] == len(keep), (s, n_out[s], len(keep))
+        assert np.array_equal(X[base[s]:base[s] + n_out[s]], b[keep]), s
 
 
 def _brute_force_keep(P, r, nb):

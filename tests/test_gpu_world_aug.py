@@ -325,3 +325,26 @@ def test_end_to_end_from_the_database_to_the_encoder_and_the_targets(tmp_path):
     for key in ta:
         for x, y in zip(ta[key], tb[key]):
             assert x.tobytes() == y.tobytes(), key
+
+
+def test_more_chunks_than_one_pass_of_the_offset_scan():
+    """Just over 1024 x 1024 rows of 4 columns in three scenes, the range mask on: 1025 chunks of 1024 rows, each with
+    its own kept count, so the one workgroup that scans the chunk counts 1024 at a time carries its running total
+    into a second pass (the last chunk's offset, and n_kept)."""
+    rng = np.random.default_rng(41)
+    sizes = [400000, 300000, 1024 * 1024 + 700 - 700000]
+    assert (sum(sizes) + 1023) // 1024 > 1024                                              # what the test is for
+    box = np.array([[1.0, 2.0, -1.0, 4.0, 2.0, 1.5, 0.3]], np.float32)
+    ops = []
+    for b, n in enumerate(sizes):
+        p = np.empty((n, 4), np.float32)
+        p[:, :2] = rng.uniform(-50, 50, (n, 2))
+        p[:, 2] = rng.uniform(-3, 1, n)
+        p[:, 3] = rng.random(n)
+        drawn = {'flips': [('x', b == 1), ('y', b == 2)], 'noise_rot': 0.3 - 0.25 * b, 'noise_scale': 0.95 + 0.05 * b,
+                 'noise_translate': np.array([[0.5, -0.25, 0.1]], np.float32) * b}
+        ops.append((p, box, np.ones(1, np.int32), drawn))
+    pc_range = np.array([-40.0, -40.0, -3.0, 40.0, 40.0, 1.0], np.float32)
+    want = R.batch(ops, pc_range)
+    assert 0.5 < len(want[0]) / sum(sizes) < 0.8 and want[2][-1] > 1024                    # rows drop everywhere
+    _check_against_restatement(_run(ops, pc_range), want, sum(sizes))
