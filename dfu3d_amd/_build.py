@@ -33,7 +33,8 @@ def _deps():
     return (sources() + glob.glob(os.path.join(CSRC, "*.hpp")) + glob.glob(os.path.join(CSRC, "*.inc"))
             + [os.path.join(INCLUDE, "dfu3d.h"), os.path.join(INCLUDE, "dfu3d_vfe.h"),
                os.path.join(INCLUDE, "dfu3d_head.h"), os.path.join(INCLUDE, "dfu3d_post.h"),
-               os.path.join(INCLUDE, "dfu3d_aug.h"), os.path.join(INCLUDE, "dfu3d_bev.h")])
+               os.path.join(INCLUDE, "dfu3d_aug.h"), os.path.join(INCLUDE, "dfu3d_bev.h"),
+               os.path.join(INCLUDE, "dfu3d_opt.h")])
 
 
 def _stale(out):

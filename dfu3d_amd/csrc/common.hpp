@@ -233,6 +233,19 @@ __device__ __forceinline__ int block_sum_i(int v, int *s_w) {
   return t;
 }
 
+// The same for a double: the waves by wave_sum_d, then the NW wave sums in wave order -- a fixed shape, so the bits of the
+// result depend on the values and their threads only.  s_w: NW doubles of LDS, same rule as block_sum_i's.
+template <int NW>
+__device__ __forceinline__ double block_sum_d(double v, double *s_w) {
+  v = wave_sum_d(v);
+  if (lane_id() == 0) s_w[threadIdx.x >> 6] = v;
+  __syncthreads();
+  double t = s_w[0];
+#pragma unroll
+  for (int w = 1; w < NW; w++) t += s_w[w];
+  return t;
+}
+
 // ---- calibration arithmetic -------------------------------------------------
 // calibration_kitti.py:104-112, float32: sequential-k FMA chain (== sgemm).
 __device__ __forceinline__ void lidar_to_rect_f32(const float *M, float x, float y,
