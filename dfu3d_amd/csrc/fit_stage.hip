@@ -8,9 +8,11 @@
 //      ordered by their smallest index.  Here: one workgroup per instance, a
 //      lock-free union-find whose roots are always the smallest index of their
 //      set (atomicMin link), parents / group summaries / group boxes in LDS.
-// a14  rectangle_fitting.py:83-159: 89 candidate headings; one wave per heading,
-//      lanes stride the cluster's points, three sweeps (extent, mean, variance)
-//      with fp64 wave reductions; first strict maximum wins.
+// a14  rectangle_fitting.py:83-159: 89 candidate headings, searched in two tiers: every heading is scored in two
+//      sweeps (extents; sums, sums of squares and counts), and only the headings whose score lies within a
+//      band of the best one are re-scored with the reference's three sweeps (extent, mean, variance); first
+//      strict maximum wins.  Three size classes: a wave per cluster with a lane per heading (up to 64 members),
+//      a workgroup per cluster with the members in LDS, a workgroup per (cluster, batch of headings).
 // a15  my_loader.py:633-702: box from the rectangle, fp64.
 #include "common.hpp"
 
@@ -838,25 +840,6 @@ constexpr int FW = FT / 64;
 constexpr int MAXTH = 128;
 constexpr int LDS_MEMBERS = 2048;   // clusters up to this size: members cached in LDS, one wave per heading
 
-// block-wide reduction of K per-thread doubles (sum / min / max by OP): result in out[0..K)
-struct OpSum { __device__ static double f(double a, double b) { return a + b; } };
-struct OpMin { __device__ static double f(double a, double b) { return fmin(a, b); } };
-struct OpMax { __device__ static double f(double a, double b) { return fmax(a, b); } };
-template <class OP>
-__device__ __forceinline__ double wave_red(double v) {
-#pragma unroll
-  for (int m = 32; m >= 1; m >>= 1) v = OP::f(v, shfl_xor_d(v, m));
-  return v;
-}
-
-struct Ext { double c1min, c1max, c2min, c2max; };
-
-__device__ __forceinline__ double readlane_f64(double v, int l) {   // l uniform
-  const int lo = __builtin_amdgcn_readlane(__double2loint(v), l);
-  const int hi = __builtin_amdgcn_readlane(__double2hiint(v), l);
-  return __hiloint2double(hi, lo);
-}
-
 __device__ __forceinline__ void cross_point(double a0, double a1, double b0, double b1,
                                             double c0, double c1, double &x, double &y) {
   // my_loader.py:699-702
@@ -1169,28 +1152,49 @@ __global__ __launch_bounds__(FT) void k_fit_gather(
 // tier 2 re-scores, with the reference's own three sweeps, only the headings whose tier-1 cost lies within
 // FIT_TAU * (largest mag) of the best one -- one heading unless the point set has an exact or nearly exact symmetry.
 // A heading outside that band cannot be the reference's arg-max, and inside it the reference's formula decides.
+// The arithmetic of both tiers is stated ONCE below (project, Extent, edge_dist, exact_cost, HeadingPick); the three
+// size classes differ in where a point comes from and who reduces, nothing else.
 constexpr double FIT_TAU = 1e-8;
-// v_min_f64 / v_max_f64 as they are: fmin() / fmax() on a loop-carried value make the compiler canonicalise it first
-// (v_max_f64 x, x, x per use -- a quarter of the first sweep's instructions); no signalling NaN can reach these loops
-__device__ __forceinline__ double min_raw_d(double a, double b) {
-  double r;
-  asm("v_min_f64 %0, %1, %2" : "=v"(r) : "v"(a), "v"(b));
-  return r;
+
+// a point in the frame of a heading (rectangle_fitting.py:124-126).  The operand order is the reference's: the library
+// is built without FMA contraction, so every caller gets the same bits.
+__device__ __forceinline__ void project(double x, double y, double ct, double st, double &c1, double &c2) {
+  c1 = x * ct + y * st;
+  c2 = x * (-st) + y * ct;
 }
-__device__ __forceinline__ double max_raw_d(double a, double b) {
-  double r;
-  asm("v_max_f64 %0, %1, %2" : "=v"(r) : "v"(a), "v"(b));
-  return r;
+// the extents of the projected points: a0 / a1 the smallest / largest c1, b0 / b1 of c2
+struct Extent {
+  double a0, a1, b0, b1;
+  __device__ __forceinline__ void clear() { a0 = INFINITY; a1 = -INFINITY; b0 = INFINITY; b1 = -INFINITY; }
+  // v_min_f64 / v_max_f64 as they are (tier 1): fmin() / fmax() on a loop-carried value make the compiler canonicalise
+  // it first (v_max_f64 x, x, x per use -- a quarter of the first sweep's instructions); no signalling NaN can reach
+  // these loops
+  __device__ __forceinline__ void add_raw(double c1, double c2) {
+    a0 = min_f64_raw(a0, c1); a1 = max_f64_raw(a1, c1);
+    b0 = min_f64_raw(b0, c2); b1 = max_f64_raw(b1, c2);
+  }
+  __device__ __forceinline__ void add(double c1, double c2) {       // the reference's sweeps and the final extents
+    a0 = fmin(a0, c1); a1 = fmax(a1, c1);
+    b0 = fmin(b0, c2); b1 = fmax(b1, c2);
+  }
+  __device__ __forceinline__ void wave_reduce() {
+    a0 = wave_min_d(a0); a1 = wave_max_d(a1);
+    b0 = wave_min_d(b0); b1 = wave_max_d(b1);
+  }
+};
+// distance to the nearer edge, per axis (rectangle_fitting.py:96-97); d1 < d2 puts the point into E1, else into E2
+__device__ __forceinline__ void edge_dist(const Extent &e, double c1, double c2, double &d1, double &d2) {
+  d1 = fmin(fabs(e.a1 - c1), fabs(c1 - e.a0));
+  d2 = fmin(fabs(e.b1 - c2), fabs(c2 - e.b0));
 }
 struct FitAcc {                                   // tier 1, second sweep
   double s1, s2, q1, q2;
   int n1, n2;
   __device__ __forceinline__ void clear() { s1 = s2 = q1 = q2 = 0.0; n1 = n2 = 0; }
-  __device__ __forceinline__ void add(double x, double y, double ct, double st, double a0, double a1, double b0, double b1) {
-    const double c1 = x * ct + y * st;
-    const double c2 = x * (-st) + y * ct;
-    const double d1 = fmin(fabs(a1 - c1), fabs(c1 - a0));
-    const double d2 = fmin(fabs(b1 - c2), fabs(c2 - b0));
+  __device__ __forceinline__ void add(double x, double y, double ct, double st, const Extent &e) {
+    double c1, c2, d1, d2;
+    project(x, y, ct, st, c1, c2);
+    edge_dist(e, c1, c2, d1, d2);
     // the squares are summed with an FMA: the SPLIT is the reference's to the bit, the summation of the variance is
     // tier 1's own (the band covers it).  (An fp64 comparison issues at the rate of an addition -- tools/micro/
     // cmp_rates.hip -- so the sign of d1 - d2 instead of the comparison only added an instruction.)
@@ -1208,67 +1212,170 @@ struct FitAcc {                                   // tier 1, second sweep
     return V1 + V2;
   }
 };
-// the reference's cost of one heading, a wave over the points (lanes take points lane, lane + 64, ...): three sweeps
-__device__ __forceinline__ double wave_exact_cost(const double *mx, const double *my, int m, double ct, double st) {
-  const int lane = lane_id();
-  double a0 = INFINITY, a1 = -INFINITY, b0 = INFINITY, b1 = -INFINITY;
-  for (int i = lane; i < m; i += 64) {
-    const double x = mx[i], y = my[i];
-    const double c1 = x * ct + y * st;
-    const double c2 = x * (-st) + y * ct;
-    a0 = fmin(a0, c1); a1 = fmax(a1, c1);
-    b0 = fmin(b0, c2); b1 = fmax(b1, c2);
-  }
-  a0 = wave_min_d(a0); a1 = wave_max_d(a1);
-  b0 = wave_min_d(b0); b1 = wave_max_d(b1);
+
+// Where exact_cost takes a cluster's points from, and who adds up.
+// A wave over memory (LDS or global): lanes take points lane, lane + 64, ...; extents, sums and counts are wave-reduced.
+struct WavePoints {
+  const double *mx, *my;
+  int m;
+  template <class F>
+  __device__ __forceinline__ void each(F f) const { for (int i = lane_id(); i < m; i += 64) f(mx[i], my[i]); }
+  __device__ __forceinline__ void reduce(Extent &e) const { e.wave_reduce(); }
+  __device__ __forceinline__ double sum(double v) const { return wave_sum_d(v); }
+  __device__ __forceinline__ int sum(int v) const { return wave_sum_i(v); }
+};
+// A lane over registers: lane j holds member j (m <= 64), every lane walks all of them through broadcasts as scalar
+// operands and scores a heading of its own; nothing to reduce.
+struct LanePoints {
+  double x, y;
+  int m;
+  template <class F>
+  __device__ __forceinline__ void each(F f) const { for (int j = 0; j < m; j++) f(rl_d(x, j), rl_d(y, j)); }
+  __device__ __forceinline__ void reduce(Extent &) const {}
+  __device__ __forceinline__ double sum(double v) const { return v; }
+  __device__ __forceinline__ int sum(int v) const { return v; }
+};
+// the reference's cost of one heading, three sweeps (rectangle_fitting.py:83-111): extents; means of E1 / E2; variances
+template <class Points>
+__device__ __forceinline__ double exact_cost(const Points &p, double ct, double st) {
+  Extent e;
+  e.clear();
+  p.each([&](double x, double y) {
+    double c1, c2;
+    project(x, y, ct, st, c1, c2);
+    e.add(c1, c2);
+  });
+  p.reduce(e);
   double s1 = 0.0, s2 = 0.0;
   int n1 = 0, n2 = 0;
-  for (int i = lane; i < m; i += 64) {
-    const double x = mx[i], y = my[i];
-    const double c1 = x * ct + y * st;
-    const double c2 = x * (-st) + y * ct;
-    const double d1 = fmin(fabs(a1 - c1), fabs(c1 - a0));
-    const double d2 = fmin(fabs(b1 - c2), fabs(c2 - b0));
+  p.each([&](double x, double y) {
+    double c1, c2, d1, d2;
+    project(x, y, ct, st, c1, c2);
+    edge_dist(e, c1, c2, d1, d2);
     if (d1 < d2) { s1 += d1; n1++; } else { s2 += d2; n2++; }
-  }
-  s1 = wave_sum_d(s1); s2 = wave_sum_d(s2);
-  n1 = wave_sum_i(n1); n2 = wave_sum_i(n2);
+  });
+  s1 = p.sum(s1); s2 = p.sum(s2);
+  n1 = p.sum(n1); n2 = p.sum(n2);
   const double m1 = n1 ? s1 / (double)n1 : 0.0, m2 = n2 ? s2 / (double)n2 : 0.0;
   double q1 = 0.0, q2 = 0.0;
-  for (int i = lane; i < m; i += 64) {
-    const double x = mx[i], y = my[i];
-    const double c1 = x * ct + y * st;
-    const double c2 = x * (-st) + y * ct;
-    const double d1 = fmin(fabs(a1 - c1), fabs(c1 - a0));
-    const double d2 = fmin(fabs(b1 - c2), fabs(c2 - b0));
+  p.each([&](double x, double y) {
+    double c1, c2, d1, d2;
+    project(x, y, ct, st, c1, c2);
+    edge_dist(e, c1, c2, d1, d2);
     if (d1 < d2) { const double u = d1 - m1; q1 += u * u; }
     else { const double u = d2 - m2; q2 += u * u; }
-  }
-  q1 = wave_sum_d(q1); q2 = wave_sum_d(q2);
+  });
+  q1 = p.sum(q1); q2 = p.sum(q2);
   double V1 = 0.0, V2 = 0.0;
   if (n1) V1 = -(q1 / (double)n1);
   if (n2) V2 = -(q2 / (double)n2);
   return V1 + V2;
 }
-// From the tier-1 costs of all headings (cost[th], th < n_theta) and the largest mag: the arg-max of the reference.
-// Whole wave, uniform; mx / my: the cluster's points (LDS or global); ctab / stab: cos / sin of the headings.
+
+// The band rule: from the tier-1 costs of all headings, the arg-max of the reference.  open() with the largest tier-1
+// cost and the largest mag; count() every heading whose cost is in_band(); then offer() the in-band headings in
+// ascending order, each with its exact cost if rescore() says so and with its tier-1 cost otherwise; result().
+// (Where the lanes hold different headings -- k_fit_tiny -- wave_combine() comes before result().)
+struct HeadingPick {
+  double band, bestc;
+  int ncand, bestth;
+  __device__ __forceinline__ void open(double top, double mag_max) {
+    band = top - FIT_TAU * mag_max;
+    bestc = -INFINITY;
+    bestth = 0x7FFFFFFF;
+    ncand = 0;
+  }
+  __device__ __forceinline__ bool in_band(double tier1_cost) const { return tier1_cost >= band; }
+  __device__ __forceinline__ void count(int n) { ncand += n; }
+  // the usual case is one heading in the band: it is the arg-max, no tier 2
+  __device__ __forceinline__ bool rescore() const { return ncand > 1; }
+  // first strict maximum (rectangle_fitting.py:135-136): the headings come in ascending order
+  __device__ __forceinline__ void offer(int th, double c) { if (bestc < c) { bestc = c; bestth = th; } }
+  // over the lanes: the largest cost, the smallest heading among equals; a lane without any has
+  // bestc = -inf / bestth = INT_MAX and loses against everything
+  __device__ __forceinline__ void wave_combine() {
+#pragma unroll
+    for (int msk = 32; msk >= 1; msk >>= 1) {
+      const double oc = shfl_xor_d(bestc, msk);
+      const int ot = __shfl_xor(bestth, msk, 64);
+      if (oc > bestc || (oc == bestc && ot < bestth)) { bestc = oc; bestth = ot; }
+    }
+  }
+  // (no heading with a cost that is a number: the loop of the reference never updates its initial choice, heading 0)
+  __device__ __forceinline__ int result() const { return bestth == 0x7FFFFFFF ? 0 : bestth; }
+};
+// Whole wave, uniform: cost[th], th < n_theta, the tier-1 costs; mx / my: the cluster's points (LDS or global);
+// ctab / stab: cos / sin of the headings.
 __device__ __forceinline__ int wave_pick_heading(const double *cost, int n_theta, double mag_max, const double *mx,
                                                  const double *my, int m, const double *ctab, const double *stab) {
   double top = -INFINITY;
   for (int th = 0; th < n_theta; th++) { const double c = cost[th]; if (top < c) top = c; }
-  const double band = top - FIT_TAU * mag_max;
-  int first = -1, ncand = 0;
+  HeadingPick pick;
+  pick.open(top, mag_max);
+  int first = -1;
   for (int th = 0; th < n_theta; th++)
-    if (cost[th] >= band) { if (first < 0) first = th; ncand++; }
-  if (ncand <= 1) return first < 0 ? 0 : first;          // (no heading with a cost that is a number: the reference keeps heading 0)
-  int best = 0;
-  double bc = -INFINITY;
-  for (int th = first; th < n_theta; th++) {             // uniform: the candidates, with the reference's formula
-    if (!(cost[th] >= band)) continue;
-    const double c = wave_exact_cost(mx, my, m, ctab[th], stab[th]);
-    if (bc < c) { bc = c; best = th; }
+    if (pick.in_band(cost[th])) { if (first < 0) first = th; pick.count(1); }
+  if (!pick.rescore()) {
+    if (first >= 0) pick.offer(first, cost[first]);
+    return pick.result();
   }
-  return best;
+  const WavePoints pts{mx, my, m};
+  for (int th = first; th < n_theta; th++)               // uniform: the candidates, with the reference's formula
+    if (pick.in_band(cost[th])) pick.offer(th, exact_cost(pts, ctab[th], stab[th]));
+  return pick.result();
+}
+
+__device__ __forceinline__ void fill_heading_table(double *s_ct, double *s_st, double dtheta) {
+  if (threadIdx.x < MAXTH) {                   // (rectangle_fitting.py:119-122)
+    const double theta = (double)threadIdx.x * dtheta;
+    s_ct[threadIdx.x] = cos(theta);
+    s_st[threadIdx.x] = sin(theta);
+  }
+}
+// The next item of a persistent workgroup, from a counter in the workspace header (zeroed with it); whole workgroup,
+// two barriers: the first one says that the previous item is done with s_item and with its other LDS.
+// Every lane of wave 0 adds 1 (ONE atomic of +64): the counter runs in units of 64.  (An atomic under `lane == 0`
+// whose result steers the loop invites the compiler to split the loop by lane: it hangs.)
+__device__ __forceinline__ int next_item(int *counter, int *s_item) {
+  __syncthreads();
+  if ((threadIdx.x >> 6) == 0) {
+    const int ticket = atomicAdd(counter, 1);
+    if (lane_id() == 0) *s_item = ticket >> 6;
+  }
+  __syncthreads();
+  return *s_item;
+}
+// The end of a cluster in an FT-thread workgroup: extents at the best heading (rectangle_fitting.py:139-157), combined
+// over the waves through s_ext, and the row of the cluster with descriptor dsc.  Whole workgroup, one barrier.
+__device__ __forceinline__ void fit_finish(const double *mx, const double *my, int m, const double *dsc, int best,
+                                           double dtheta, double (*s_ext)[4], int max_inst, const ViewCalib *calib,
+                                           const int *inst_class, const int *inst_is_car, const float *inst_box,
+                                           const float *inst_score, double car_aspect_max, int cap_rows, double *rows,
+                                           int *n_rows, uint32_t *status) {
+  const int wave = threadIdx.x >> 6;
+  const double thb = (double)best * dtheta;
+  const double sin_s = sin(thb), cos_s = cos(thb);
+  Extent e;
+  e.clear();
+  for (int i = threadIdx.x; i < m; i += FT) {
+    double c1, c2;
+    project(mx[i], my[i], cos_s, sin_s, c1, c2);
+    e.add(c1, c2);
+  }
+  e.wave_reduce();
+  if (lane_id() == 0) { s_ext[wave][0] = e.a0; s_ext[wave][1] = e.a1; s_ext[wave][2] = e.b0; s_ext[wave][3] = e.b1; }
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    double c1min = s_ext[0][0], c1max = s_ext[0][1], c2min = s_ext[0][2], c2max = s_ext[0][3];
+    for (int w = 1; w < FW; w++) {
+      c1min = fmin(c1min, s_ext[w][0]); c1max = fmax(c1max, s_ext[w][1]);
+      c2min = fmin(c2min, s_ext[w][2]); c2max = fmax(c2max, s_ext[w][3]);
+    }
+    const int s = (int)dsc[0], kc = (int)dsc[1], root = (int)dsc[2];
+    const int v = s / max_inst, jinst = s - v * max_inst;
+    emit_box(thb, sin_s, cos_s, c1min, c1max, c2min, c2max, dsc[5], s, v, jinst, kc, root, m, calib, inst_class,
+             inst_is_car, inst_box, inst_score, car_aspect_max, cap_rows, rows, n_rows, status);
+  }
 }
 
 // ---- F2a: clusters of at most 64 points, one wave each, one lane per heading -----
@@ -1291,6 +1398,7 @@ __global__ __launch_bounds__(256) void k_fit_tiny(
     if (m > 64) continue;
     const long long P = (long long)d[4];
     const double x = (lane < m) ? gsx[P + lane] : 0.0, y = (lane < m) ? gsy[P + lane] : 0.0;
+    const LanePoints pts{x, y, m};
     // tier 1: this lane's headings (lane, lane + 64), two sweeps each
     constexpr int TH_PER_LANE = MAXTH / 64;
     double c1t[TH_PER_LANE], magmax = 0.0, top = -INFINITY;
@@ -1301,17 +1409,16 @@ __global__ __launch_bounds__(256) void k_fit_tiny(
       if (64 * k >= n_theta) continue;                 // uniform
       const double theta = (double)th * dtheta;
       const double ct = cos(theta), st = sin(theta);
-      double a0 = INFINITY, a1 = -INFINITY, b0 = INFINITY, b1 = -INFINITY;
-      for (int j = 0; j < m; j++) {
-        const double xj = readlane_f64(x, j), yj = readlane_f64(y, j);
-        const double c1 = xj * ct + yj * st;
-        const double c2 = xj * (-st) + yj * ct;
-        a0 = min_raw_d(a0, c1); a1 = max_raw_d(a1, c1);
-        b0 = min_raw_d(b0, c2); b1 = max_raw_d(b1, c2);
-      }
+      Extent ext;
+      ext.clear();
+      pts.each([&](double xj, double yj) {
+        double c1, c2;
+        project(xj, yj, ct, st, c1, c2);
+        ext.add_raw(c1, c2);
+      });
       FitAcc A;
       A.clear();
-      for (int j = 0; j < m; j++) A.add(readlane_f64(x, j), readlane_f64(y, j), ct, st, a0, a1, b0, b1);
+      pts.each([&](double xj, double yj) { A.add(xj, yj, ct, st, ext); });
       double mag;
       const double c = A.cost(mag);
       if (th < n_theta) {
@@ -1320,97 +1427,45 @@ __global__ __launch_bounds__(256) void k_fit_tiny(
         if (mag > magmax) magmax = mag;                // (a NaN never wins)
       }
     }
-    top = wave_max_d(top);
-    magmax = wave_max_d(magmax);
-    const double band = top - FIT_TAU * magmax;
-    double bestc = -INFINITY;
-    int bestth = 0x7FFFFFFF;
-    {
-      int ncand = 0;
+    HeadingPick pick;
+    pick.open(wave_max_d(top), wave_max_d(magmax));
 #pragma unroll
-      for (int k = 0; k < TH_PER_LANE; k++) ncand += __popcll(__ballot(c1t[k] >= band));
-      if (ncand <= 1) {                                // the usual case: one heading in the band -- it is the arg-max
+    for (int k = 0; k < TH_PER_LANE; k++) pick.count(__popcll(__ballot(pick.in_band(c1t[k]))));
 #pragma unroll
-        for (int k = 0; k < TH_PER_LANE; k++)
-          if (c1t[k] >= band) { bestc = c1t[k]; bestth = lane + 64 * k; }
-      } else {
-        // tier 2: the candidates with the reference's three sweeps, each on its own lane
-#pragma unroll
-        for (int k = 0; k < TH_PER_LANE; k++) {
-          if (__ballot(c1t[k] >= band) == 0ull) continue;    // uniform
-          const int th = lane + 64 * k;
-          const double theta = (double)th * dtheta;
-          const double ct = cos(theta), st = sin(theta);
-          double a0 = INFINITY, a1 = -INFINITY, b0 = INFINITY, b1 = -INFINITY;
-          for (int j = 0; j < m; j++) {
-            const double xj = readlane_f64(x, j), yj = readlane_f64(y, j);
-            const double c1 = xj * ct + yj * st;
-            const double c2 = xj * (-st) + yj * ct;
-            a0 = fmin(a0, c1); a1 = fmax(a1, c1);
-            b0 = fmin(b0, c2); b1 = fmax(b1, c2);
-          }
-          double s1 = 0.0, s2 = 0.0;
-          int n1 = 0, n2 = 0;
-          for (int j = 0; j < m; j++) {
-            const double xj = readlane_f64(x, j), yj = readlane_f64(y, j);
-            const double c1 = xj * ct + yj * st;
-            const double c2 = xj * (-st) + yj * ct;
-            const double d1 = fmin(fabs(a1 - c1), fabs(c1 - a0));
-            const double d2 = fmin(fabs(b1 - c2), fabs(c2 - b0));
-            if (d1 < d2) { s1 += d1; n1++; } else { s2 += d2; n2++; }
-          }
-          const double m1 = n1 ? s1 / (double)n1 : 0.0, m2 = n2 ? s2 / (double)n2 : 0.0;
-          double q1 = 0.0, q2 = 0.0;
-          for (int j = 0; j < m; j++) {
-            const double xj = readlane_f64(x, j), yj = readlane_f64(y, j);
-            const double c1 = xj * ct + yj * st;
-            const double c2 = xj * (-st) + yj * ct;
-            const double d1 = fmin(fabs(a1 - c1), fabs(c1 - a0));
-            const double d2 = fmin(fabs(b1 - c2), fabs(c2 - b0));
-            if (d1 < d2) { const double u = d1 - m1; q1 += u * u; }
-            else { const double u = d2 - m2; q2 += u * u; }
-          }
-          double V1 = 0.0, V2 = 0.0;
-          if (n1) V1 = -(q1 / (double)n1);
-          if (n2) V2 = -(q2 / (double)n2);
-          const double c = V1 + V2;
-          // this lane's headings come in ascending order: keep the first strict maximum
-          if (c1t[k] >= band && bestc < c) { bestc = c; bestth = th; }
-        }
+    for (int k = 0; k < TH_PER_LANE; k++) {            // this lane's headings come in ascending order
+      if (__ballot(pick.in_band(c1t[k])) == 0ull) continue;    // uniform
+      const int th = lane + 64 * k;
+      double c = c1t[k];
+      if (pick.rescore()) {                            // tier 2: the candidates, each on its own lane
+        const double theta = (double)th * dtheta;
+        c = exact_cost(pts, cos(theta), sin(theta));
       }
+      if (pick.in_band(c1t[k])) pick.offer(th, c);
     }
-    // first strict maximum over the candidate headings (rectangle_fitting.py:135-136): the largest
-    // cost, the smallest heading among equals; a lane without any has
-    // bestc = -inf / bestth = INT_MAX and loses against everything, and if nobody has one
-    // the loop of the reference never updates its initial choice, heading 0
-#pragma unroll
-    for (int msk = 32; msk >= 1; msk >>= 1) {
-      const double oc = shfl_xor_d(bestc, msk);
-      const int ot = __shfl_xor(bestth, msk, 64);
-      if (oc > bestc || (oc == bestc && ot < bestth)) { bestc = oc; bestth = ot; }
-    }
-    const int best = (bestth == 0x7FFFFFFF) ? 0 : bestth;
+    pick.wave_combine();
+    const int best = pick.result();
     const double thb = (double)best * dtheta;
     const double sin_s = sin(thb), cos_s = cos(thb);
-    double a0 = INFINITY, a1 = -INFINITY, b0 = INFINITY, b1 = -INFINITY;
+    Extent ext;
+    ext.clear();
     if (lane < m) {
-      const double c1 = x * cos_s + y * sin_s;
-      const double c2 = x * (-sin_s) + y * cos_s;
-      a0 = c1; a1 = c1; b0 = c2; b1 = c2;
+      double c1, c2;
+      project(x, y, cos_s, sin_s, c1, c2);
+      ext = Extent{c1, c1, c2, c2};
     }
-    a0 = wave_min_d(a0); a1 = wave_max_d(a1);
-    b0 = wave_min_d(b0); b1 = wave_max_d(b1);
+    ext.wave_reduce();
     if (lane == 0) {
       const int s = (int)d[0], kc = (int)d[1], root = (int)d[2];
       const int v = s / max_inst, jinst = s - v * max_inst;
-      emit_box(thb, sin_s, cos_s, a0, a1, b0, b1, d[5], s, v, jinst, kc, root, m, calib, inst_class,
+      emit_box(thb, sin_s, cos_s, ext.a0, ext.a1, ext.b0, ext.b1, d[5], s, v, jinst, kc, root, m, calib, inst_class,
                inst_is_car, inst_box, inst_score, car_aspect_max, cap_rows, rows, n_rows, status);
     }
   }
 }
 
 // ---- F2b: clusters of 65 .. LDS_MEMBERS points, one workgroup each ---------------
-// (64 registers, no scratch: four workgroups per compute unit instead of three, 271 -> 256 us)
+// (64 registers for four workgroups per compute unit instead of three, 271 -> 256 us; the price as measured by
+// tools/isa_mix.py: one spilled VGPR, 8 bytes of scratch)
 __global__ __launch_bounds__(FT, 8) void k_fit_medium(
     const double *__restrict__ gsx, const double *__restrict__ gsy, int max_inst,
     const ViewCalib *__restrict__ calib, const int *__restrict__ inst_class,
@@ -1424,23 +1479,12 @@ __global__ __launch_bounds__(FT, 8) void k_fit_medium(
   const FitWs W = fit_ws_view(fit_ws, cap_rows, cap_big);
   const int nq = min(W.counters[0], W.cap_q);
   const int wave = threadIdx.x >> 6, lane = lane_id();
-  if (threadIdx.x < MAXTH) {                   // heading table (rectangle_fitting.py:119-122)
-    const double theta = (double)threadIdx.x * dtheta;
-    s_ct[threadIdx.x] = cos(theta);
-    s_st[threadIdx.x] = sin(theta);
-  }
+  fill_heading_table(s_ct, s_st, dtheta);
   __shared__ int s_item;
   while (true) {
-    // descriptors are handed out through a counter (the spare word of the workspace header, zeroed with it): a cluster of
-    // 2 000 members costs thirty times one of 65, and a fixed share of the queue per workgroup ended with a few workgroups
-    // busy (the fit stage 1.120 -> 1.090 ms)
-    __syncthreads();                             // the previous item is done with s_item and the members in LDS
-    if (wave == 0) {
-      const int ticket = atomicAdd(&W.counters[3], 1);        // every lane adds 1: the counter runs in units of 64 (see k_fit_big_cost)
-      if (lane == 0) s_item = ticket >> 6;
-    }
-    __syncthreads();
-    const int e = s_item;
+    // descriptors are handed out through a counter: a cluster of 2 000 members costs thirty times one of 65, and a fixed
+    // share of the queue per workgroup ended with a few workgroups busy (the fit stage 1.120 -> 1.090 ms)
+    const int e = next_item(&W.counters[3], &s_item);
     if (e >= nq) break;
     const double *d = W.dsc + (size_t)8 * e;
     const int m = (int)d[3];
@@ -1456,27 +1500,23 @@ __global__ __launch_bounds__(FT, 8) void k_fit_medium(
     for (int th0 = 2 * wave; th0 < n_theta; th0 += 2 * FW) {
       const int th1 = min(th0 + 1, n_theta - 1);       // (an odd heading count: the last one is scored twice)
       const double ct0 = s_ct[th0], st0 = s_st[th0], ct1 = s_ct[th1], st1 = s_st[th1];
-      double a0 = INFINITY, a1 = -INFINITY, b0 = INFINITY, b1 = -INFINITY;
-      double e0 = INFINITY, e1 = -INFINITY, f0 = INFINITY, f1 = -INFINITY;
+      Extent e0, e1;
+      e0.clear(); e1.clear();
       for (int i = lane; i < m; i += 64) {
         const double x = mx[i], y = my[i];
-        double c1 = x * ct0 + y * st0;
-        double c2 = x * (-st0) + y * ct0;
-        a0 = min_raw_d(a0, c1); a1 = max_raw_d(a1, c1);
-        b0 = min_raw_d(b0, c2); b1 = max_raw_d(b1, c2);
-        c1 = x * ct1 + y * st1;
-        c2 = x * (-st1) + y * ct1;
-        e0 = min_raw_d(e0, c1); e1 = max_raw_d(e1, c1);
-        f0 = min_raw_d(f0, c2); f1 = max_raw_d(f1, c2);
+        double c1, c2;
+        project(x, y, ct0, st0, c1, c2);
+        e0.add_raw(c1, c2);
+        project(x, y, ct1, st1, c1, c2);
+        e1.add_raw(c1, c2);
       }
-      a0 = wave_min_d(a0); a1 = wave_max_d(a1); b0 = wave_min_d(b0); b1 = wave_max_d(b1);
-      e0 = wave_min_d(e0); e1 = wave_max_d(e1); f0 = wave_min_d(f0); f1 = wave_max_d(f1);
+      e0.wave_reduce(); e1.wave_reduce();
       FitAcc A, B;
       A.clear(); B.clear();
       for (int i = lane; i < m; i += 64) {
         const double x = mx[i], y = my[i];
-        A.add(x, y, ct0, st0, a0, a1, b0, b1);
-        B.add(x, y, ct1, st1, e0, e1, f0, f1);
+        A.add(x, y, ct0, st0, e0);
+        B.add(x, y, ct1, st1, e1);
       }
       A.wave_reduce(); B.wave_reduce();
       double magA, magB;
@@ -1488,41 +1528,14 @@ __global__ __launch_bounds__(FT, 8) void k_fit_medium(
     double magmax = 0.0;
     for (int th = 0; th < n_theta; th++) { const double g = s_mag[th]; if (g > magmax) magmax = g; }
     const int best = wave_pick_heading(s_cost, n_theta, magmax, mx, my, m, s_ct, s_st);
-    // extents at the best heading (rectangle_fitting.py:139-157)
-    const double thb = (double)best * dtheta;
-    const double sin_s = sin(thb), cos_s = cos(thb);
-    {
-      double a0 = INFINITY, a1 = -INFINITY, b0 = INFINITY, b1 = -INFINITY;
-      for (int i = threadIdx.x; i < m; i += FT) {
-        const double x = mx[i], y = my[i];
-        const double c1 = x * cos_s + y * sin_s;
-        const double c2 = x * (-sin_s) + y * cos_s;
-        a0 = fmin(a0, c1); a1 = fmax(a1, c1);
-        b0 = fmin(b0, c2); b1 = fmax(b1, c2);
-      }
-      a0 = wave_min_d(a0); a1 = wave_max_d(a1);
-      b0 = wave_min_d(b0); b1 = wave_max_d(b1);
-      if (lane == 0) { s_ext[wave][0] = a0; s_ext[wave][1] = a1; s_ext[wave][2] = b0; s_ext[wave][3] = b1; }
-    }
-    __syncthreads();
-    if (threadIdx.x == 0) {
-      double c1min = s_ext[0][0], c1max = s_ext[0][1], c2min = s_ext[0][2], c2max = s_ext[0][3];
-      for (int w = 1; w < FW; w++) {
-        c1min = fmin(c1min, s_ext[w][0]); c1max = fmax(c1max, s_ext[w][1]);
-        c2min = fmin(c2min, s_ext[w][2]); c2max = fmax(c2max, s_ext[w][3]);
-      }
-      const int s = (int)d[0], kc = (int)d[1], root = (int)d[2];
-      const int v = s / max_inst, jinst = s - v * max_inst;
-      emit_box(thb, sin_s, cos_s, c1min, c1max, c2min, c2max, d[5], s, v, jinst, kc, root, m, calib,
-               inst_class, inst_is_car, inst_box, inst_score, car_aspect_max, cap_rows, rows,
-               n_rows, status);
-    }
+    fit_finish(mx, my, m, d, best, dtheta, s_ext, max_inst, calib, inst_class, inst_is_car, inst_box, inst_score,
+               car_aspect_max, cap_rows, rows, n_rows, status);
   }
 }
 
 // ---- large clusters: workgroup per (cluster, batch of BIGC_HB headings), items handed out through a counter ----
-// The workgroup streams the cluster's members through LDS in chunks of BIGC_CH (three sweeps: extents; sums and counts
-// of E1 / E2; squared deviations -- rectangle_fitting.py:83-111); every wave scores BIGC_HPW headings of the batch
+// The workgroup streams the cluster's members through LDS in chunks of BIGC_CH (tier 1's two sweeps: extents; sums,
+// sums of squares and counts of E1 / E2); every wave scores BIGC_HPW headings of the batch
 // against each chunk with everything per heading in registers.  No LDS operand besides the two coordinates, no
 // workgroup-wide reduction: the only barriers are the two around a chunk's load.
 // (First formulation: eight headings per sweep, every thread other points -- 64 accumulators per lane, two waves
@@ -1541,24 +1554,12 @@ __global__ __launch_bounds__(BIGC_T) void k_fit_big_cost(const double *__restric
   const FitWs W = fit_ws_view(fit_ws, cap_rows, cap_big);
   const int nbig = min(W.counters[1], cap_big);
   if (nbig == 0) return;
-  if (threadIdx.x < MAXTH) {                   // heading table (rectangle_fitting.py:119-122)
-    const double theta = (double)threadIdx.x * dtheta;
-    s_ct[threadIdx.x] = cos(theta);
-    s_st[threadIdx.x] = sin(theta);
-  }
+  fill_heading_table(s_ct, s_st, dtheta);
   const int wave = threadIdx.x >> 6, lane = lane_id();
   const int nb = (n_theta + BIGC_HB - 1) / BIGC_HB;
   const int items = nbig * nb;
   while (true) {
-    __syncthreads();                           // the previous item is done with s_item and the chunk
-    if (wave == 0) {
-      // every lane of wave 0 adds 1 (ONE atomic of +64): the counter runs in units of 64.  (An atomic under
-      // `lane == 0` whose result steers the loop invites the compiler to split the loop by lane: it hangs.)
-      const int ticket = atomicAdd(&W.counters[2], 1);
-      if (lane == 0) s_item = ticket >> 6;
-    }
-    __syncthreads();
-    const int ticket_item = s_item;
+    const int ticket_item = next_item(&W.counters[2], &s_item);
     if (ticket_item >= 3 * items) break;       // uniform; the counter only grows
     // Three rounds of tickets, longest clusters first: an item of a 50 000-point cluster runs for a good part of this
     // kernel's duration and must not be among the last to start (1.20 -> 0.94 ms; giving the long clusters finer items
@@ -1571,16 +1572,16 @@ __global__ __launch_bounds__(BIGC_T) void k_fit_big_cost(const double *__restric
     if ((m > BIGC_LONG ? 0 : (m > BIGC_MID ? 1 : 2)) != round) continue;   // (uniform) not this round's
     const double *mx = gsx + (long long)dsc[4], *my = gsy + (long long)dsc[4];
     int th[BIGC_HPW];
-    double ct[BIGC_HPW], st[BIGC_HPW], nst[BIGC_HPW];
+    double ct[BIGC_HPW], st[BIGC_HPW];
 #pragma unroll
     for (int h = 0; h < BIGC_HPW; h++) {
       th[h] = tb + wave * BIGC_HPW + h;
       const int tc = min(th[h], n_theta - 1);  // a heading past the end is scored and dropped
-      ct[h] = s_ct[tc]; st[h] = s_st[tc]; nst[h] = -st[h];
+      ct[h] = s_ct[tc]; st[h] = s_st[tc];
     }
-    double a0[BIGC_HPW], a1[BIGC_HPW], b0[BIGC_HPW], b1[BIGC_HPW];
+    Extent ext[BIGC_HPW];
 #pragma unroll
-    for (int h = 0; h < BIGC_HPW; h++) { a0[h] = INFINITY; a1[h] = -INFINITY; b0[h] = INFINITY; b1[h] = -INFINITY; }
+    for (int h = 0; h < BIGC_HPW; h++) ext[h].clear();
     for (int c0 = 0; c0 < m; c0 += BIGC_CH) {
       const int cm = min(BIGC_CH, m - c0);
       __syncthreads();
@@ -1590,18 +1591,14 @@ __global__ __launch_bounds__(BIGC_T) void k_fit_big_cost(const double *__restric
         const double x = lx[i], y = ly[i];
 #pragma unroll
         for (int h = 0; h < BIGC_HPW; h++) {
-          const double c1 = x * ct[h] + y * st[h];
-          const double c2 = x * nst[h] + y * ct[h];
-          a0[h] = min_raw_d(a0[h], c1); a1[h] = max_raw_d(a1[h], c1);
-          b0[h] = min_raw_d(b0[h], c2); b1[h] = max_raw_d(b1[h], c2);
+          double c1, c2;
+          project(x, y, ct[h], st[h], c1, c2);
+          ext[h].add_raw(c1, c2);
         }
       }
     }
 #pragma unroll
-    for (int h = 0; h < BIGC_HPW; h++) {
-      a0[h] = wave_min_d(a0[h]); a1[h] = wave_max_d(a1[h]);
-      b0[h] = wave_min_d(b0[h]); b1[h] = wave_max_d(b1[h]);
-    }
+    for (int h = 0; h < BIGC_HPW; h++) ext[h].wave_reduce();
     FitAcc A[BIGC_HPW];
 #pragma unroll
     for (int h = 0; h < BIGC_HPW; h++) A[h].clear();
@@ -1613,7 +1610,7 @@ __global__ __launch_bounds__(BIGC_T) void k_fit_big_cost(const double *__restric
       for (int i = lane; i < cm; i += 64) {
         const double x = lx[i], y = ly[i];
 #pragma unroll
-        for (int h = 0; h < BIGC_HPW; h++) A[h].add(x, y, ct[h], st[h], a0[h], a1[h], b0[h], b1[h]);
+        for (int h = 0; h < BIGC_HPW; h++) A[h].add(x, y, ct[h], st[h], ext[h]);
       }
     }
 #pragma unroll
@@ -1640,47 +1637,17 @@ __global__ __launch_bounds__(FT) void k_fit_big_box(
   __shared__ double s_ct[MAXTH], s_st[MAXTH];
   const FitWs W = fit_ws_view(fit_ws, cap_rows, cap_big);
   const int nbig = min(W.counters[1], cap_big);
-  if (threadIdx.x < MAXTH) {                   // heading table (rectangle_fitting.py:119-122)
-    const double theta = (double)threadIdx.x * dtheta;
-    s_ct[threadIdx.x] = cos(theta);
-    s_st[threadIdx.x] = sin(theta);
-  }
+  fill_heading_table(s_ct, s_st, dtheta);
   for (int c = blockIdx.x; c < nbig; c += gridDim.x) {
-  __syncthreads();
-  const double *dsc = W.dsc + (size_t)8 * W.big_list[c];
-  const int s = (int)dsc[0], kc = (int)dsc[1], root = (int)dsc[2], m = (int)dsc[3];
-  const double zmax = dsc[5];
-  const double *mx = gsx + (long long)dsc[4], *my = gsy + (long long)dsc[4];
-  const double *cost = W.big_cost + (size_t)c * MAXTH;
-  const int wave = threadIdx.x >> 6, lane = lane_id();
-  // the arg-max of the reference: tier-1 costs of k_fit_big_cost, the headings within the band re-scored with the
-  // reference's three sweeps (one heading, unless the cluster has a symmetry); every wave computes the same answer
-  const int best = wave_pick_heading(cost, n_theta, dsc[7], mx, my, m, s_ct, s_st);
-  const double thb = (double)best * dtheta;
-  const double sin_s = sin(thb), cos_s = cos(thb);
-  double a0 = INFINITY, a1 = -INFINITY, b0 = INFINITY, b1 = -INFINITY;
-  for (int i = threadIdx.x; i < m; i += FT) {
-    const double x = mx[i], y = my[i];
-    const double c1 = x * cos_s + y * sin_s;
-    const double c2 = x * (-sin_s) + y * cos_s;
-    a0 = fmin(a0, c1); a1 = fmax(a1, c1);
-    b0 = fmin(b0, c2); b1 = fmax(b1, c2);
-  }
-  a0 = wave_min_d(a0); a1 = wave_max_d(a1);
-  b0 = wave_min_d(b0); b1 = wave_max_d(b1);
-  if (lane == 0) { s_ext[wave][0] = a0; s_ext[wave][1] = a1; s_ext[wave][2] = b0; s_ext[wave][3] = b1; }
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    double c1min = s_ext[0][0], c1max = s_ext[0][1], c2min = s_ext[0][2], c2max = s_ext[0][3];
-    for (int w = 1; w < FW; w++) {
-      c1min = fmin(c1min, s_ext[w][0]); c1max = fmax(c1max, s_ext[w][1]);
-      c2min = fmin(c2min, s_ext[w][2]); c2max = fmax(c2max, s_ext[w][3]);
-    }
-    const int v = s / max_inst, jinst = s - v * max_inst;
-    emit_box(thb, sin_s, cos_s, c1min, c1max, c2min, c2max, zmax, s, v, jinst, kc, root, m, calib,
-             inst_class, inst_is_car, inst_box, inst_score, car_aspect_max, cap_rows, rows, n_rows,
-             status);
-  }
+    __syncthreads();
+    const double *dsc = W.dsc + (size_t)8 * W.big_list[c];
+    const int m = (int)dsc[3];
+    const double *mx = gsx + (long long)dsc[4], *my = gsy + (long long)dsc[4];
+    // the arg-max of the reference: tier-1 costs of k_fit_big_cost, the headings within the band re-scored with the
+    // reference's three sweeps (one heading, unless the cluster has a symmetry); every wave computes the same answer
+    const int best = wave_pick_heading(W.big_cost + (size_t)c * MAXTH, n_theta, dsc[7], mx, my, m, s_ct, s_st);
+    fit_finish(mx, my, m, dsc, best, dtheta, s_ext, max_inst, calib, inst_class, inst_is_car, inst_box, inst_score,
+               car_aspect_max, cap_rows, rows, n_rows, status);
   }
 }
 

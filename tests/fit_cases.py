@@ -100,6 +100,66 @@ def edge_size_cases():
     return out
 
 
+TIE_SIZES = (64, 65, 2048, 2049, 4097)                  # k_fit_tiny | k_fit_medium, LDS | big list, a second staging chunk
+TIE_HEADINGS = ((2.0, 44), (1.0, 89), (0.75, 119), (0.7, 128))   # (dtheta_deg, headings)
+TIE_FOLD = 60
+# (headings, case): (heading index of the oracle, of the library) where the two pick DIFFERENT members of the tied set --
+# measured on the library as it was before the tie test existed and unchanged since.  The tied costs agree to the last
+# bits and the library's three sweeps add up in another order than numpy's (lanes striding the points against pairwise
+# sums), so either index is an arg-max of "the reference's formula"; which one numpy lands on is not reproducible on the
+# GPU.  These combinations are left out of the GPU test (tests/test_gpu_fit_edges.py), the other fourteen are in it.
+TIE_DISAGREE = {(44, "tie64"): (14, 29), (44, "tie4097"): (2, 5), (89, "tie64"): (28, 58),
+                (119, "tie64"): (101, 77), (119, "tie2049"): (103, 63), (119, "tie4097"): (61, 5)}
+
+
+def ring_tie_cases():
+    """One instance per member count in TIE_SIZES, one cluster each: concentric regular 60-gons with a random phase per
+    ring, radii in (0.4, 2.4] m, and the n mod 60 points left over exactly on the common centre.  The set is invariant
+    under turns of 6 degrees, so at every heading count of TIE_HEADINGS several headings share the best cost up to the
+    last bits: the search has to go through tier 2, the band rule and the reference's three-sweep cost."""
+    out = []
+    for n in TIE_SIZES:
+        rng = np.random.default_rng(n)
+        cx, cy = 10.0 + n % 7, -4.0
+        k, extra = divmod(n, TIE_FOLD)
+        parts = []
+        for i in range(k):
+            a = rng.uniform(0, 2 * np.pi) + 2 * np.pi * np.arange(TIE_FOLD) / TIE_FOLD
+            r = 0.4 + 2.0 * (i + 1) / k
+            parts.append(np.stack([cx + r * np.cos(a), cy + r * np.sin(a)], 1))
+        parts.append(np.tile([[cx, cy]], (extra, 1)))
+        out.append(FitCase("tie%d" % n, np.vstack(parts), [n], True, _seg_class(n)))
+    return out
+
+
+def ring_tie_cases_at(n_theta):
+    """The ring cases the GPU test runs at this heading count: all but those of TIE_DISAGREE."""
+    return [c for c in ring_tie_cases() if (n_theta, c.name) not in TIE_DISAGREE]
+
+
+def tier1_band(pts, dtheta_deg, tau=1e-8):
+    """The indices of the headings that the two-tier search of fit_stage.hip re-scores: a float64 restatement of its
+    two-sweep cost (variance = q/n - (s/n)^2 of the edge distances of E1 / E2) and of the band `tau * largest mag` under
+    the best cost."""
+    dtheta = np.deg2rad(dtheta_deg)
+    x, y = pts[:, 0], pts[:, 1]
+    cost, mag = [], []
+    for theta in np.arange(0.0, np.pi / 2.0 - dtheta, dtheta):
+        ct, st = np.cos(theta), np.sin(theta)
+        c1, c2 = x * ct + y * st, x * (-st) + y * ct
+        d1 = np.minimum(np.abs(c1.max() - c1), np.abs(c1 - c1.min()))
+        d2 = np.minimum(np.abs(c2.max() - c2), np.abs(c2 - c2.min()))
+        v = m = 0.0
+        for e in (d1[d1 < d2], d2[~(d1 < d2)]):
+            if len(e):
+                v -= np.mean(e * e) - np.mean(e) ** 2
+                m += np.mean(e * e)
+        cost.append(v)
+        mag.append(m)
+    cost = np.array(cost)
+    return np.nonzero(cost >= cost.max() - tau * max(mag))[0]
+
+
 # ---------------------------------------------------------------------------------------------------- (b)
 def long_cases():
     """[0]: 16 385 points, one cluster.  [1]: one cluster of 16 384, one of 300 and twelve singletons, interleaved."""

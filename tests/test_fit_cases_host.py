@@ -14,6 +14,7 @@ def _all_cases():
     cases = F.edge_size_cases() + F.long_cases() + [F.many_cluster_case(), F.singleton_case()]
     cases += F.asym_far_cases() + F.asym_near_cases()
     cases += [F.fallback_case(n) for n in F.FALLBACK_SIZES]
+    cases += F.ring_tie_cases()
     return cases
 
 
@@ -60,3 +61,32 @@ def test_the_cases_cover_what_they_are_named_for():
         assert {c.n_clusters for c in fam} == {1, 2} and all(c.grid_ok == ok for c in fam)
     assert [F.fallback_case(n).n for n in F.FALLBACK_SIZES] == [300, 4096, 4097, 61440, 61441]
     assert not any(F.fallback_case(n).grid_ok for n in F.FALLBACK_SIZES)
+
+
+@pytest.mark.parametrize("dtheta_deg,n_theta", F.TIE_HEADINGS)
+def test_ring_ties_put_more_than_one_heading_in_the_band(dtheta_deg, n_theta):
+    """Every (case, heading count) of the tie test has at least two headings within the band of the two-tier search, so
+    the GPU test cannot pass without tier 2; each case is ONE cluster under the default R0, Rd.  Above 64 headings the
+    in-band set reaches into the second heading slot of a lane of k_fit_tiny."""
+    assert O.Params().dtheta_deg == 1.0 and (F.FitCase.R0, F.FitCase.Rd) == (O.Params().R0, O.Params().Rd)
+    assert len(np.arange(0.0, np.pi / 2.0 - np.deg2rad(dtheta_deg), np.deg2rad(dtheta_deg))) == n_theta
+    cases = F.ring_tie_cases()
+    assert [c.sizes for c in cases] == [[n] for n in (64, 65, 2048, 2049, 4097)]
+    for c in cases:
+        assert (c.R0, c.Rd) == (F.FitCase.R0, F.FitCase.Rd)
+        lab = O.range_cluster_labels(c.pts[:, 0], c.pts[:, 1], c.R0, c.Rd)
+        assert not lab.any(), c.name                                 # one cluster, root 0
+        band = F.tier1_band(c.pts, dtheta_deg)
+        assert len(band) >= 2, (c.name, n_theta, band)
+        if n_theta > 64:
+            assert band.max() >= 64, (c.name, n_theta, band)
+        if (n_theta, c.name) in F.TIE_DISAGREE:                      # both indices are members of the tied set
+            assert set(F.TIE_DISAGREE[n_theta, c.name]) <= set(band.tolist()), (c.name, n_theta, band)
+
+
+def test_the_ring_ties_left_out_leave_every_size_and_heading_count_covered():
+    kept = {n: [c.name for c in F.ring_tie_cases_at(n)] for _, n in F.TIE_HEADINGS}
+    assert sum(len(v) for v in kept.values()) == 20 - len(F.TIE_DISAGREE) == 14
+    assert all(len(v) >= 2 for v in kept.values())
+    assert set().union(*kept.values()) == {"tie%d" % n for n in F.TIE_SIZES}
+    assert "tie64" in kept[128]                                      # the second heading slot of k_fit_tiny's lanes

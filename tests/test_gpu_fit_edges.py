@@ -2,9 +2,10 @@
 the CPU oracle: cluster sizes around the three fit kernels, the LDS chunk and the scheduling rounds; segments in every
 launch class; more than 512 / 1 024 clusters in one instance (passes of k_fit_gather, whose own contract on sx / sy /
 sroot is checked directly); links that only the farther point's radius makes; the three forms of the point-level
-fallback; heading counts up to the table's last entry; row and descriptor overflow.  The instances are planted in
-tests/fit_cases.py (their properties are checked on the CPU by tests/test_fit_cases_host.py); integers, memberships,
-member counts, roots and heading indices must be equal, fp64 geometry within 1e-9, all 24 row columns compared."""
+fallback; heading counts up to the table's last entry, with and without ties between headings; row and descriptor
+overflow.  The instances are planted in tests/fit_cases.py (their properties are checked on the CPU by
+tests/test_fit_cases_host.py); integers, memberships, member counts, roots and heading indices must be equal, fp64
+geometry within 1e-9, all 24 row columns compared."""
 import numpy as np
 import pytest
 import torch
@@ -257,6 +258,26 @@ def test_heading_counts(st, dtheta_deg, n_expected):
     exp, labels = inst.expected(O.Params(dtheta_deg=dtheta_deg))
     _check_labels(r, inst, labels)
     assert r.n == len(exp) == 3
+    F.assert_rows_match(r.R[:r.n], exp, dtheta)
+
+
+@pytest.mark.parametrize("dtheta_deg,n_expected", F.TIE_HEADINGS)
+def test_heading_ties_on_the_size_edges_at_every_heading_count(st, dtheta_deg, n_expected):
+    """Point sets invariant under turns of 6 degrees (F.ring_tie_cases: 14 or 15 headings within the band at 44, 89 and
+    119 headings, two at 128, indices of 64 and more among them -- tests/test_fit_cases_host.py) with exactly 64 | 65,
+    2 048 | 2 049 and 4 097 members: tier 2, the band rule and the three-sweep cost in every fit kernel, in the second
+    heading slot of a lane of k_fit_tiny and in a second staging chunk of k_fit_big_cost.  The reference's arg-max as an
+    index, all 24 columns.  Six of the twenty (case, heading count) are left out: there the library and numpy land on
+    different members of the tied set (F.TIE_DISAGREE has the indices)."""
+    cases = F.ring_tie_cases_at(n_expected)
+    inst = _Instances([c.pts for c in cases], 4, 31)
+    n_theta, dtheta = _thetas(dtheta_deg)
+    assert n_theta == n_expected
+    r = _fit(st, inst, n_theta, dtheta, 16)
+    assert r.st == 0 and r.guards_intact
+    exp, labels = inst.expected(O.Params(dtheta_deg=dtheta_deg))
+    _check_labels(r, inst, labels)
+    assert exp[:, 17].astype(int).tolist() == [c.n for c in cases] and r.n == len(exp)
     F.assert_rows_match(r.R[:r.n], exp, dtheta)
 
 
