@@ -1,5 +1,5 @@
 """The box conversions between a detector's LiDAR boxes and KITTI result rows (pcdet/utils/box_utils.py:203-288), used
-by generate_prediction_dicts.  Host NumPy on a few hundred boxes per frame, as in the reference; same dtypes (float32
+by generate_prediction_dicts, and from a label's camera box to the LiDAR frame (:134-150), used by KittiDataset.  Host NumPy on a few hundred boxes per frame, as in the reference; same dtypes (float32
 corner offsets, the rotation in the dtype of the boxes)."""
 import numpy as np
 
@@ -50,3 +50,14 @@ def boxes3d_kitti_camera_to_imageboxes(boxes3d, calib, image_shape=None):
         boxes[:, 0::2] = np.clip(boxes[:, 0::2], a_min=0, a_max=image_shape[1] - 1)
         boxes[:, 1::2] = np.clip(boxes[:, 1::2], a_min=0, a_max=image_shape[0] - 1)
     return boxes
+
+
+def boxes3d_kitti_camera_to_lidar(boxes3d_camera, calib):
+    """(N,7) [x y z l h w ry] in the rectified camera frame, y at the box bottom -> (N,7) [x y z dx dy dz heading], the
+    centre in the LiDAR frame (box_utils.py:134-150).  The input is not written."""
+    b = np.array(boxes3d_camera, copy=True)
+    r = b[:, 6:7]
+    l, h, w = b[:, 3:4], b[:, 4:5], b[:, 5:6]
+    xyz_lidar = calib.rect_to_lidar(b[:, 0:3])
+    xyz_lidar[:, 2] += h[:, 0] / 2
+    return np.concatenate([xyz_lidar, l, w, h, -(r + np.pi / 2)], axis=-1)

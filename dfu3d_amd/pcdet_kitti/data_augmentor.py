@@ -64,8 +64,16 @@ def class_ids(names, class_names):
     return np.array([class_names.index(n) + 1 if n in class_names else 0 for n in names], np.int32)
 
 
+def _on_device(points):
+    """A scene's points handed in as a tensor on the GPU (the batched FOV ingest's output) rather than as NumPy."""
+    return isinstance(points, torch.Tensor) and points.is_cuda
+
+
 def _check_scene(points, boxes, what):
-    if not isinstance(points, np.ndarray) or points.ndim != 2 or points.dtype != np.float32 or points.shape[1] < 3:
+    if _on_device(points):
+        if points.dim() != 2 or points.dtype != torch.float32 or points.shape[1] < 3:
+            raise Dfu3dError("%s: points on the device must be (n, C >= 3) float32" % what)
+    elif not isinstance(points, np.ndarray) or points.ndim != 2 or points.dtype != np.float32 or points.shape[1] < 3:
         raise Dfu3dError("%s: points must be (n, C >= 3) float32" % what)
     if not isinstance(boxes, np.ndarray) or boxes.ndim != 2 or boxes.shape[1] not in (7, 9):
         raise Dfu3dError("%s: gt_boxes must be (N, 7) or (N, 9), got %s" % (what, getattr(boxes, 'shape', None)))
@@ -235,8 +243,12 @@ def _pack_host(data_dicts, class_names, device):
         raise Dfu3dError("prepare_batch: the scenes' point columns, box columns and box dtypes must agree")
     npts = np.array([len(p) for p in pts], np.int64)
     nbox = np.array([len(b) for b in boxes], np.int64)
+    if any(_on_device(p) for p in pts):                   # scenes already on the device: concatenated there
+        points = torch.cat([p.to(device) if _on_device(p) else _h2d(p, device) for p in pts], 0)
+    else:
+        points = _h2d(np.concatenate(pts, 0), device)
     return {
-        'points': _h2d(np.concatenate(pts, 0), device),
+        'points': points,
         'point_off': _h2d(np.concatenate([[0], np.cumsum(npts)]).astype(np.int64), device),
         'boxes': _h2d(np.concatenate(boxes, 0), device),
         'box_off': _h2d(np.concatenate([[0], np.cumsum(nbox)]).astype(np.int32), device),
@@ -270,7 +282,9 @@ def prepare_batch(data_dicts, augmentor, processor, class_names, training=True, 
     """B scenes -> the model's batch_dict on the device: `points` (sum n, 1 + C) with the batch index in column 0,
     `gt_boxes` (B, max_gt, 8|10) zero-padded with the class id last, `batch_size`, `gt_cnt` (B).
 
-    data_dicts: NumPy dicts (points, gt_boxes, gt_names[, gt_boxes_mask]).  With a `gt_sampling` entry (and training)
+    data_dicts: NumPy dicts (points, gt_boxes, gt_names[, gt_boxes_mask]); a scene's `points` may also be a float32
+    tensor on the GPU (KittiDataset.batches hands the FOV ingest's output over so), concatenated on the device then.
+    With a `gt_sampling` entry (and training)
     they go through DataBaseSampler.sample_batch first and stay on the device from there.  One draw per scene
     (augmentor.draw_world_params), then one launch chain.  augmentor None: no augmentation.
     Default: ONE host read (n_kept, the B box counts and the status words together) to cut points[:n_kept] and

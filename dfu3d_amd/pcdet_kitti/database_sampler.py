@@ -212,7 +212,10 @@ class DataBaseSampler(object):
         if gt_boxes.dtype not in (np.float32, np.float64):
             raise Dfu3dError("gt_sampling: gt_boxes must be float32 or float64")
         pts = d['points']
-        if pts.dtype != np.float32 or pts.ndim != 2:
+        if isinstance(pts, torch.Tensor):                 # a scene already on the device (upload_batch concatenates there)
+            if not pts.is_cuda or pts.dtype != torch.float32 or pts.dim() != 2:
+                raise Dfu3dError("gt_sampling: points given as a tensor must be (n, C) float32 on the GPU")
+        elif pts.dtype != np.float32 or pts.ndim != 2:
             raise Dfu3dError("gt_sampling: points must be (n, C) float32")
         if pts.shape[1] != self.num_point_features:
             raise Dfu3dError("gt_sampling: NUM_POINT_FEATURES %d != the scene's %d point columns"
@@ -265,12 +268,17 @@ class DataBaseSampler(object):
         def h2d(a):
             return torch.from_numpy(np.ascontiguousarray(a)).to(self.device)
         # never an empty point tensor (a null pointer): one spare row when the batch has no points
-        pts = np.concatenate([s['points'] for s in sc] + [np.zeros((0 if npts.sum() else 1, C), np.float32)], 0)
+        spare = np.zeros((0 if npts.sum() else 1, C), np.float32)
+        if any(isinstance(s['points'], torch.Tensor) for s in sc):
+            pts_d = torch.cat([s['points'].to(self.device) if isinstance(s['points'], torch.Tensor) else h2d(s['points'])
+                               for s in sc] + [h2d(spare)], 0)
+        else:
+            pts_d = h2d(np.concatenate([s['points'] for s in sc] + [spare], 0))
         obj_cnt = cat('obj_cnt', (0,), np.int32)
         return {
             'scenes': sc, 'max_boxes': max_boxes, 'max_points': int(npts.max()) if B else 0,
             'cap': int(npts.sum()) + int(obj_cnt.astype(np.int64).sum()),      # no scene can outgrow its bound
-            'points': h2d(pts), 'pt_off': h2d(np.concatenate([[0], np.cumsum(npts)]).astype(np.int64)),
+            'points': pts_d, 'pt_off': h2d(np.concatenate([[0], np.cumsum(npts)]).astype(np.int64)),
             'box_off': h2d(np.concatenate([[0], np.cumsum(nbox)]).astype(np.int32)),
             'gt_cnt': h2d(np.array([s['n_gt'] for s in sc], np.int32)),
             'boxes': h2d(cat('boxes', (0, 7), np.float64)), 'grp': h2d(cat('grp', (0,), np.int32)),
