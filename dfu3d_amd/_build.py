@@ -34,7 +34,8 @@ def _deps():
             + [os.path.join(INCLUDE, "dfu3d.h"), os.path.join(INCLUDE, "dfu3d_vfe.h"),
                os.path.join(INCLUDE, "dfu3d_head.h"), os.path.join(INCLUDE, "dfu3d_post.h"),
                os.path.join(INCLUDE, "dfu3d_aug.h"), os.path.join(INCLUDE, "dfu3d_bev.h"),
-               os.path.join(INCLUDE, "dfu3d_opt.h"), os.path.join(INCLUDE, "dfu3d_ingest.h")])
+               os.path.join(INCLUDE, "dfu3d_opt.h"), os.path.join(INCLUDE, "dfu3d_ingest.h"),
+               os.path.join(INCLUDE, "dfu3d_pn2.h")])
 
 
 def _stale(out):

@@ -1,0 +1,421 @@
+"""The PointNet++ ops of csrc/pointnet2_stage.hip and the PointNet2MSG backbone on the GPU, against the NumPy float32
+restatements of tests/pointnet2_ref.py, plain-torch formulations on the same device and golden G19.  Every comparison is
+an equality unless its test says otherwise."""
+import copy
+
+import numpy as np
+import pytest
+
+from tests import pointnet2_ref as R
+from tests.test_oracle_pointnet2 import g19, levels, meta_of  # noqa: F401
+
+pytestmark = pytest.mark.gpu
+
+EPS32 = float(np.finfo(np.float32).eps)
+
+
+def cu(a):
+    import torch
+    return torch.from_numpy(np.ascontiguousarray(a)).cuda()
+
+
+def with_status(fn, *args, **kwargs):
+    """fn(*args) inside a status scope -> (result, status bits)."""
+    import torch
+    from dfu3d_amd import pointnet2_ops as ops
+    st = torch.zeros(1, dtype=torch.int32, device='cuda')
+    with ops.status_scope(st):
+        res = fn(*args, **kwargs)
+    return res, int(st.item())
+
+
+def run_fps(xyz, npoint):
+    from dfu3d_amd import pointnet2_ops as ops
+    (idx, new_xyz), st = with_status(ops.fps, cu(xyz), npoint)
+    return idx.cpu().numpy(), new_xyz.cpu().numpy(), st
+
+
+# ---- farthest point sampling -------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("case", R.FPS_CASES + [R.FPS_LEVEL1, R.FPS_BIG], ids=str)
+def test_fps_matches_the_restatement(case):
+    from dfu3d_amd import pointnet2_ops as ops
+    B, N, npoint = case
+    assert (N > ops.FPS_ONCHIP) == (case == R.FPS_BIG)
+    xyz = R.cloud(1900 + N, B, N)
+    want_idx, want_xyz = R.fps(xyz, npoint)
+    idx, new_xyz, st = run_fps(xyz, npoint)
+    assert st == 0 and idx.dtype == np.int32
+    assert np.array_equal(idx, want_idx)
+    assert np.array_equal(new_xyz, want_xyz)
+    if case in (R.FPS_CASES[-1], R.FPS_BIG):                               # two runs give equal bits
+        idx2, new_xyz2, _ = run_fps(xyz, npoint)
+        assert np.array_equal(idx, idx2) and np.array_equal(new_xyz.view(np.uint32), new_xyz2.view(np.uint32))
+
+
+@pytest.mark.parametrize("N", [700, R.FPS_BIG[1]])
+def test_fps_ties_take_the_lowest_index(N):
+    """All points identical: after the first pick every step is a full tie.  Every point stored twice: the picks'
+    coordinates equal those of the deduplicated run, and the index is the lower of the pair."""
+    same = np.tile(np.asarray([[[1.5, -2.25, 0.125]]], np.float32), (2, N, 1))
+    idx, new_xyz, st = run_fps(same, 9)
+    assert st == 0 and not idx.any() and np.array_equal(new_xyz, same[:, :9])
+    half = R.cloud(77, 2, N // 2)
+    twice = np.repeat(half, 2, axis=1)
+    i1, x1, _ = run_fps(half, 40)
+    i2, x2, _ = run_fps(twice, 40)
+    assert np.array_equal(x1, x2) and np.array_equal(i2, 2 * i1)
+    assert np.array_equal(i1, R.fps(half, 40)[0]) and np.array_equal(i2, R.fps(twice, 40)[0])
+
+
+@pytest.mark.parametrize("N", [300, R.FPS_BIG[1]])
+def test_fps_non_finite_coordinate_sets_the_status_and_stays_in_range(N):
+    from dfu3d_amd import pointnet2_ops as ops
+    for bad in (np.nan, np.inf):
+        xyz = R.cloud(5, 2, N)
+        xyz[1, N // 2, 1] = bad
+        idx, _, st = run_fps(xyz, 50)
+        assert st == ops.ST_BAD_POINT
+        assert idx.min() >= 0 and idx.max() < N and not idx[:, 0].any()
+        assert np.array_equal(idx[0], R.fps(xyz[:1], 50)[0][0])            # the clean sample is not affected
+
+
+# ---- ball query -------------------------------------------------------------------------------------------------------
+def run_ball(xyz, ctr, radii, nsamples):
+    from dfu3d_amd import pointnet2_ops as ops
+    return [i.cpu().numpy() for i in ops.ball_query(cu(xyz), cu(ctr), radii, nsamples)]
+
+
+@pytest.mark.parametrize("M", R.BALL_M)
+@pytest.mark.parametrize("N", R.BALL_N)
+def test_ball_query_matches_the_restatement(N, M):
+    xyz = R.cloud(10 + N, 2, N, scale=1.0)
+    ctr = R.cloud(20 + M, 2, M, scale=1.0)
+    ctr[:, 0] = xyz[:, N // 2]                                             # one centre on a point
+    scales = [(1e-4, 5), (0.9, 7), (1.7, 16)] + [(1e3, ns) for ns in R.BALL_NSAMPLE_ALL]
+    want = {s: R.ball_query(xyz, ctr, *s) for s in scales}
+    nothing = want[(1e-4, 5)]
+    assert not nothing[:, 1:].any() and np.array_equal(nothing[:, 0], np.full((2, 5), N // 2))
+    for ns in R.BALL_NSAMPLE_ALL:                                          # everything: 0, 1, 2, ..., then the first hit, 0
+        assert np.array_equal(want[(1e3, ns)][0, 0], np.where(np.arange(ns) < N, np.arange(ns), 0))
+    for s in scales:
+        got, = run_ball(xyz, ctr, [s[0]], [s[1]])
+        assert got.dtype == np.int32 and np.array_equal(got, want[s]), s
+    for a, b in zip(scales[:-1], scales[1:]):                              # two scales in one launch = two launches
+        got = run_ball(xyz, ctr, [a[0], b[0]], [a[1], b[1]])
+        assert np.array_equal(got[0], want[a]) and np.array_equal(got[1], want[b]), (a, b)
+
+
+def test_ball_query_excludes_a_point_at_exactly_the_radius():
+    r = np.float32(0.5)
+    xyz = np.zeros((1, 130, 3), np.float32) + 9.0
+    xyz[0, 3] = [r, 0, 0]                                                  # d2 = 0.25 = r * r: outside
+    xyz[0, 70] = [np.nextafter(r, np.float32(0)), 0, 0]                    # inside
+    xyz[0, 129] = [0, -r, 0]                                               # outside
+    ctr = np.zeros((1, 1, 3), np.float32)
+    got, = run_ball(xyz, ctr, [0.5], [4])
+    assert got.tolist() == [[[70, 70, 70, 70]]] and np.array_equal(got, R.ball_query(xyz, ctr, 0.5, 4))
+    got2 = run_ball(xyz, ctr, [0.5, float(np.nextafter(r, np.float32(1)))], [4, 2])
+    assert got2[0].tolist() == [[[70, 70, 70, 70]]] and got2[1].tolist() == [[[3, 70]]]
+
+
+# ---- group, three_nn, interpolate: the forwards -----------------------------------------------------------------------
+@pytest.mark.parametrize("C", R.GROUP_C + [0])
+def test_group_matches_the_restatement_and_torch_gather(C):
+    import torch
+    from dfu3d_amd import pointnet2_ops as ops
+    B, N, M, ns = 2, 301, 37, 5
+    rng = np.random.default_rng(30 + C)
+    xyz, ctr = R.cloud(31, B, N), R.cloud(32, B, M)
+    feat = rng.normal(0, 1, (B, C, N)).astype(np.float32) if C else None
+    idx = rng.integers(0, N, (B, M, ns)).astype(np.int32)
+    t_xyz, t_ctr, t_idx = cu(xyz), cu(ctr), cu(idx)
+    t_feat = cu(feat) if C else None
+    long = t_idx.long().view(B, 1, M * ns)
+    for use_xyz in ((True, False) if C else (True,)):
+        got, st = with_status(ops.group, t_xyz, t_ctr, t_feat, t_idx, use_xyz)
+        assert st == 0 and tuple(got.shape) == (B, (3 if use_xyz else 0) + C, M, ns)
+        assert np.array_equal(got.cpu().numpy(), R.group(xyz, ctr, feat, idx, use_xyz))
+        parts = []
+        if use_xyz:
+            gx = torch.gather(t_xyz.transpose(1, 2).contiguous(), 2, long.expand(B, 3, M * ns)).view(B, 3, M, ns)
+            parts.append(gx - t_ctr.transpose(1, 2).unsqueeze(-1))
+        if C:
+            parts.append(torch.gather(t_feat, 2, long.expand(B, C, M * ns)).view(B, C, M, ns))
+        assert torch.equal(got, torch.cat(parts, dim=1))
+    if C:                                                                  # the reference's names
+        from dfu3d_amd.pcdet_kitti import pointnet2_utils as pu
+        assert torch.equal(pu.grouping_operation(t_feat, t_idx), ops.group(None, None, t_feat, t_idx, False))
+        assert torch.equal(pu.gather_operation(t_feat, t_idx[:, :, 0].contiguous()),
+                           torch.gather(t_feat, 2, t_idx[:, :, 0].long().unsqueeze(1).expand(B, C, M)))
+    _, st = with_status(ops.group, t_xyz, t_ctr, t_feat, torch.full_like(t_idx, N), True)
+    assert st == ops.ST_BAD_INDEX                                          # out of range: flagged, point 0 read
+
+
+@pytest.mark.parametrize("m", R.NN_M)
+def test_three_nn_and_interpolate_match_the_restatement_and_torch(m):
+    import torch
+    from dfu3d_amd import pointnet2_ops as ops
+    B, n = 2, 263
+    rng = np.random.default_rng(40 + m)
+    unknown = R.cloud(41, B, n)
+    known = R.cloud(42 + m, B, m)
+    if m >= 3:
+        known[:, m // 2:] = known[:, :m - m // 2]                          # duplicate known points: equal distances
+    unknown[:, 0] = known[:, 0]
+    want_d, want_i = R.three_nn(unknown, known)
+    dist, idx = ops.three_nn(cu(unknown), cu(known))
+    assert np.array_equal(idx.cpu().numpy(), want_i) and idx.dtype == torch.int32
+    assert np.array_equal(dist.cpu().numpy(), want_d)
+    if m < 3:
+        assert np.isinf(want_d[:, :, m:]).all() and not want_i[:, :, m:].any()
+    else:                                                                  # against torch: a stable sort of the distances
+        d = cu(unknown)[:, :, None, :] - cu(known)[:, None, :, :]
+        d = d * d
+        d2, order = torch.sort((d[..., 0] + d[..., 1]) + d[..., 2], dim=2, stable=True)
+        assert torch.equal(idx.long(), order[:, :, :3])
+        assert np.array_equal(np.sqrt(d2[:, :, :3].cpu().numpy()), want_d)  # (the root in NumPy: correctly rounded)
+    for C in R.GROUP_C:
+        feat = rng.normal(0, 1, (B, C, m)).astype(np.float32)
+        w = rng.uniform(0, 1, (B, n, 3)).astype(np.float32)
+        t_feat, t_w = cu(feat), cu(w)
+        got, st = with_status(ops.three_interpolate, t_feat, idx, t_w)
+        assert st == 0 and np.array_equal(got.cpu().numpy(), R.three_interpolate(feat, want_i, w))
+        f = [torch.gather(t_feat, 2, idx[:, :, r].long().unsqueeze(1).expand(B, C, n)) for r in range(3)]
+        ww = [t_w[:, :, r].unsqueeze(1) for r in range(3)]
+        assert torch.equal(got, (ww[0] * f[0] + ww[1] * f[1]) + ww[2] * f[2])
+
+
+# ---- the ordered backward ---------------------------------------------------------------------------------------------
+def backward_bound(grad_out, idx, N, weight, k):
+    """Per element: len * eps32 * sum |terms| of the float32 sequential sum -- derived, not measured."""
+    B, C = grad_out.shape[:2]
+    flat = idx.reshape(B, -1).astype(np.int64)
+    E = flat.shape[1]
+    bound = np.zeros((B, C, N))
+    for b in range(B):
+        vals = np.abs(grad_out.reshape(B, C, -1)[b][:, np.arange(E) // k].astype(np.float64))
+        if weight is not None:
+            vals = vals * np.abs(weight.reshape(B, E)[b].astype(np.float64))[None]
+        cnt = np.bincount(flat[b], minlength=N)
+        for c in range(C):
+            np.add.at(bound[b, c], flat[b], vals[c])
+        bound[b] *= cnt[None, :] * EPS32
+    return bound
+
+
+BWD_CASES = {
+    'random': lambda rng: rng.integers(0, 97, (2, 29, 7)),
+    'all_zero_E1024': lambda rng: np.zeros((2, 128, 8), np.int64),
+    'unreferenced': lambda rng: np.where(rng.integers(0, 97, (2, 29, 7)) == 13, 14, rng.integers(0, 97, (2, 29, 7))),
+    'long_runs': lambda rng: rng.integers(0, 3, (1, 100, 9)),
+}
+
+
+@pytest.mark.parametrize("name", sorted(BWD_CASES))
+def test_grouping_backward_is_the_ordered_sum(name):
+    import torch
+    from dfu3d_amd import pointnet2_ops as ops
+    rng = np.random.default_rng(50)
+    idx = BWD_CASES[name](rng).astype(np.int32)
+    idx[idx == 13] = 14
+    B, M, ns = idx.shape
+    N, C = 97, 19
+    feat = rng.normal(0, 1, (B, C, N)).astype(np.float32)
+    go = rng.normal(0, 1, (B, C, M, ns)).astype(np.float32)
+    want = R.gather_backward(go, idx, N)
+    t_idx = cu(idx)
+    grads = []
+    for _ in range(2):
+        t_feat = cu(feat).requires_grad_(True)
+        ops.grouping(t_feat, t_idx).backward(cu(go))
+        grads.append(t_feat.grad.cpu().numpy())
+    assert np.array_equal(grads[0].view(np.uint32), want.view(np.uint32))  # exact bits, +0.0 where nobody points
+    assert np.array_equal(grads[0].view(np.uint32), grads[1].view(np.uint32))
+    assert not grads[0][:, :, 13].view(np.uint32).any()
+    inv = ops.inverse_of(t_idx, N)
+    assert ops.inverse_of(t_idx, N) is inv                                 # built once per index tensor
+    csr, lst = inv.csr.cpu().numpy(), inv.list.cpu().numpy()
+    for b in range(B):
+        w_csr, w_lst = R.invert(idx[b].reshape(-1), N)
+        assert np.array_equal(csr[b], w_csr) and np.array_equal(lst[b], w_lst)
+    f64 = cu(feat).double().requires_grad_(True)                           # float64 plain-torch autograd
+    torch.gather(f64, 2, t_idx.long().view(B, 1, -1).expand(B, C, M * ns)).backward(cu(go).double().view(B, C, -1))
+    err = np.abs(grads[0].astype(np.float64) - f64.grad.cpu().numpy())
+    assert (err <= backward_bound(go, idx, N, None, 1)).all(), err.max()
+    xyz, ctr = cu(R.cloud(51, B, N)), cu(R.cloud(52, B, M))                # QueryAndGroup's form: xyz channels get none
+    t_feat = cu(feat).requires_grad_(True)
+    go5 = rng.normal(0, 1, (B, 3 + C, M, ns)).astype(np.float32)
+    ops.query_group(xyz, ctr, t_feat, t_idx, True).backward(cu(go5))
+    assert np.array_equal(t_feat.grad.cpu().numpy().view(np.uint32),
+                          R.gather_backward(go5[:, 3:], idx, N).view(np.uint32))
+
+
+@pytest.mark.parametrize("m", [1, 40])
+def test_interpolate_backward_is_the_ordered_weighted_sum(m):
+    import torch
+    from dfu3d_amd import pointnet2_ops as ops
+    rng = np.random.default_rng(60 + m)
+    B, C, n = 2, 21, 333
+    idx = rng.integers(0, m, (B, n, 3)).astype(np.int32)
+    if m > 20:
+        idx[idx == 7] = 8
+    w = rng.uniform(0, 1, (B, n, 3)).astype(np.float32)
+    feat = rng.normal(0, 1, (B, C, m)).astype(np.float32)
+    go = rng.normal(0, 1, (B, C, n)).astype(np.float32)
+    want = R.gather_backward(go, idx, m, weight=w, k=3)
+    t_idx, t_w = cu(idx), cu(w)
+    t_feat = cu(feat).requires_grad_(True)
+    ops.interpolate(t_feat, t_idx, t_w).backward(cu(go))
+    got = t_feat.grad.cpu().numpy()
+    assert np.array_equal(got.view(np.uint32), want.view(np.uint32))
+    if m > 20:
+        assert not got[:, :, 7].view(np.uint32).any()
+    f64 = cu(feat).double().requires_grad_(True)
+    f = [torch.gather(f64, 2, t_idx[:, :, r].long().unsqueeze(1).expand(B, C, n)) for r in range(3)]
+    sum(t_w[:, :, r].double().unsqueeze(1) * f[r] for r in range(3)).backward(cu(go).double())
+    err = np.abs(got.astype(np.float64) - f64.grad.cpu().numpy())
+    assert (err <= backward_bound(go, idx, m, w, 3)).all(), err.max()
+
+
+# ---- the backbone ---------------------------------------------------------------------------------------------------
+def make_model(g, check=True):
+    import torch
+    from dfu3d_amd.pcdet_kitti.pointnet2_backbone import PointNet2MSG
+    model = PointNet2MSG(R.G19_CFG, 3 + R.G19_EXTRA, check=check)
+    model.load_state_dict({k: torch.from_numpy(g["sd_" + k].copy()) for k in meta_of(g)["state_dict_keys"]}, strict=True)
+    return model.cuda().eval()
+
+
+def plain_forward(model, g):
+    """PointNet2MSG's forward in plain torch on the GPU, indexing with the golden's indices, with the model's weights."""
+    import torch
+    import torch.nn.functional as F
+    pts = cu(g["points"])
+    B = R.G19_B
+    l_xyz = [cu(x) for x in levels(g)]
+    l_feat = [pts[:, 4:].reshape(B, -1, R.G19_EXTRA).permute(0, 2, 1).contiguous()]
+    for k, sa in enumerate(model.SA_modules):
+        xyz, new_xyz, feat = l_xyz[k], l_xyz[k + 1], l_feat[k]
+        M, pooled = new_xyz.shape[1], []
+        for s, mlp in enumerate(sa.mlps):
+            idx = cu(g["sa%d_ball%d" % (k, s)]).long()
+            ns = idx.shape[2]
+            flat = idx.view(B, 1, M * ns)
+            gx = torch.gather(xyz.transpose(1, 2).contiguous(), 2, flat.expand(B, 3, M * ns)).view(B, 3, M, ns)
+            gx = gx - new_xyz.transpose(1, 2).unsqueeze(-1)
+            gf = torch.gather(feat, 2, flat.expand(B, feat.shape[1], M * ns)).view(B, feat.shape[1], M, ns)
+            x = mlp(torch.cat([gx, gf], dim=1))
+            pooled.append(F.max_pool2d(x, kernel_size=[1, ns]).squeeze(-1))
+        l_feat.append(torch.cat(pooled, dim=1))
+    for k in range(len(model.FP_modules) - 1, -1, -1):
+        dist, idx = cu(g["fp%d_nn_dist" % k]), cu(g["fp%d_nn_idx" % k]).long()
+        recip = 1.0 / (dist + 1e-8)
+        w = recip / recip.sum(dim=2, keepdim=True)
+        known = l_feat[k + 1]
+        C, n = known.shape[1], idx.shape[1]
+        f = [torch.gather(known, 2, idx[:, :, r].unsqueeze(1).expand(B, C, n)) for r in range(3)]
+        x = (w[:, :, 0].unsqueeze(1) * f[0] + w[:, :, 1].unsqueeze(1) * f[1]) + w[:, :, 2].unsqueeze(1) * f[2]
+        x = torch.cat([x, l_feat[k]], dim=1)
+        l_feat[k] = model.FP_modules[k].mlp(x.unsqueeze(-1)).squeeze(-1)
+    out = l_feat[0].permute(0, 2, 1).contiguous()
+    return out.view(-1, out.shape[-1])
+
+
+def test_backbone_on_g19(g19, monkeypatch):
+    import torch
+    from dfu3d_amd import pointnet2_ops as ops
+    seen = {'fps': [], 'ball': [], 'nn': []}
+    real = (ops.fps, ops.ball_query, ops.three_nn)
+
+    def rec(key, fn):
+        def wrapped(*a, **k):
+            res = fn(*a, **k)
+            seen[key].append(res)
+            return res
+        return wrapped
+    for key, fn in zip(('fps', 'ball_query', 'three_nn'), real):
+        monkeypatch.setattr(ops, key, rec({'fps': 'fps', 'ball_query': 'ball', 'three_nn': 'nn'}[key], fn))
+    model = make_model(g19)
+    with torch.no_grad():
+        res = model(dict(points=cu(g19["points"]), batch_size=R.G19_B))
+        plain = plain_forward(model, g19)
+    n_sa, n_fp = len(model.SA_modules), len(model.FP_modules)
+    assert len(seen['fps']) == n_sa and len(seen['ball']) == n_sa and len(seen['nn']) == n_fp   # one launch per module
+    for k in range(n_sa):
+        assert np.array_equal(seen['fps'][k][0].cpu().numpy(), g19["sa%d_fps_idx" % k])
+        assert np.array_equal(seen['fps'][k][1].cpu().numpy(), g19["sa%d_new_xyz" % k])
+        for s, idx in enumerate(seen['ball'][k]):
+            assert np.array_equal(idx.cpu().numpy(), g19["sa%d_ball%d" % (k, s)])
+    for j, (dist, idx) in enumerate(seen['nn']):                           # the deepest level first
+        k = n_fp - 1 - j
+        assert np.array_equal(idx.cpu().numpy(), g19["fp%d_nn_idx" % k])
+        assert np.array_equal(dist.cpu().numpy(), g19["fp%d_nn_dist" % k])
+    assert np.array_equal(res['point_coords'].cpu().numpy(), g19["point_coords"])
+    feats = res['point_features']
+    assert tuple(feats.shape) == g19["point_features"].shape and model.num_point_features == feats.shape[1]
+    assert torch.equal(feats, plain)                                       # bit for bit
+    dev_hip = float(np.abs(feats.cpu().numpy() - g19["point_features"]).max())
+    dev_torch = float(np.abs(plain.cpu().numpy() - g19["point_features"]).max())
+    print("deviation from the golden's CPU values: HIP backbone %.3g, plain torch on the GPU %.3g" % (dev_hip, dev_torch))
+    assert dev_hip <= 4.0 * dev_torch
+
+
+def test_backbone_flags_a_row_of_the_wrong_sample(g19):
+    from dfu3d_amd._lib import Dfu3dError
+    pts = g19["points"].copy()
+    pts[300, 0] = 0.0
+    with pytest.raises(Dfu3dError, match="does not belong"):
+        make_model(g19)(dict(points=cu(pts), batch_size=R.G19_B))
+    model = make_model(g19, check=False)
+    model(dict(points=cu(pts), batch_size=R.G19_B))                        # unchecked: the word is there to be read
+    from dfu3d_amd import pointnet2_ops as ops
+    assert int(model.status.item()) == ops.ST_BAD_BATCH
+
+
+def test_training_step_is_finite_non_zero_and_repeatable(g19):
+    """One training step at G19's shape, twice from the same state: every parameter gradient finite, non-zero for every
+    conv weight, bit-equal between the runs.  The ops of this stage repeat their bits (the tests above); torch's own
+    convolutions are asked for their deterministic algorithms: with torch's default choice the two runs differed by
+    1 to 4 units in the last place (SA_modules.0.mlps.0.0.weight: 259.05035 against 259.0503)."""
+    import torch
+    base = make_model(g19)
+    pts = cu(g19["points"])
+    runs = []
+    before = torch.backends.cudnn.deterministic
+    torch.backends.cudnn.deterministic = True       # torch's own convolutions: only algorithms that repeat their sums
+    try:
+        for _ in range(2):
+            model = copy.deepcopy(base).train()
+            out = model(dict(points=pts, batch_size=R.G19_B))['point_features']
+            (out * out).sum().backward()
+            runs.append({k: p.grad.detach().cpu().numpy() for k, p in model.named_parameters()})
+    finally:
+        torch.backends.cudnn.deterministic = before
+    assert runs[0] and set(runs[0]) == {k for k, _ in base.named_parameters()}
+    for k, g in runs[0].items():
+        assert np.isfinite(g).all(), k
+        if g.ndim == 4:
+            assert np.abs(g).max() > 0, k                                  # every conv weight
+        assert np.array_equal(g.view(np.uint32), runs[1][k].view(np.uint32)), k
+
+
+def test_forward_without_check_makes_no_host_read(g19):
+    """No synchronisation and no device-to-host copy in the forward and the backward (check=False): torch's sync debug
+    mode raises on any synchronising call of torch's own; the library itself never synchronises (include/dfu3d.h)."""
+    import torch
+    model = make_model(g19, check=False).train()
+    pts = cu(g19["points"])
+
+    def step():
+        out = model(dict(points=pts, batch_size=R.G19_B))['point_features']
+        (out * out).sum().backward()
+        return out
+    step()                                                                 # library loaded, allocator warm
+    torch.cuda.synchronize()
+    torch.cuda.set_sync_debug_mode("error")
+    try:
+        out = step()
+    finally:
+        torch.cuda.set_sync_debug_mode("default")
+    torch.cuda.synchronize()
+    assert bool(torch.isfinite(out).all()) and int(model.status.item()) == 0
