@@ -55,6 +55,35 @@ __device__ __forceinline__ int block_rank(bool flag, int *s_w, int &block_total)
   return off + r;
 }
 
+// The register of lane `lane`, in every lane.  PRECONDITION of the whole family: `lane` is wave-uniform and in 0..63.
+// This is v_readlane_b32 (one per 32 bits), a register read and not a shuffle: an index that differs from lane to lane
+// gives every lane the value ONE of them asked for.
+__device__ __forceinline__ int readlane_i(int v, int lane) { return __builtin_amdgcn_readlane(v, lane); }
+__device__ __forceinline__ float readlane_f(float v, int lane) { return __int_as_float(readlane_i(__float_as_int(v), lane)); }
+__device__ __forceinline__ double readlane_d(double v, int lane) {
+  return __hiloint2double(readlane_i(__double2hiint(v), lane), readlane_i(__double2loint(v), lane));
+}
+__device__ __forceinline__ unsigned long long readlane_u64(unsigned long long v, int lane) {
+  const unsigned lo = (unsigned)readlane_i((int)(v & 0xFFFFFFFFull), lane);
+  const unsigned hi = (unsigned)readlane_i((int)(v >> 32), lane);
+  return ((unsigned long long)hi << 32) | lo;
+}
+// The exchange of a 64-bit value through the LDS path (ds_bpermute), as two 32-bit ones: any lane index, one per lane.
+// PRECONDITION: the lane read from is active (__shfl's own).  (The high half widens with its sign, as in
+// __hiloint2double: the shift drops the copies.)
+__device__ __forceinline__ unsigned long long shfl_xor_u64(unsigned long long v, int mask) {
+  int lo = (int)(v & 0xFFFFFFFFull), hi = (int)(v >> 32);
+  lo = __shfl_xor(lo, mask, 64);
+  hi = __shfl_xor(hi, mask, 64);
+  return ((unsigned long long)hi << 32) | (unsigned)lo;
+}
+__device__ __forceinline__ unsigned long long shfl_u64(unsigned long long v, int lane) {
+  int lo = (int)(v & 0xFFFFFFFFull), hi = (int)(v >> 32);
+  lo = __shfl(lo, lane, 64);
+  hi = __shfl(hi, lane, 64);
+  return ((unsigned long long)hi << 32) | (unsigned)lo;
+}
+
 // Register moves between lanes without the LDS path: data-parallel-primitive modifiers.  A lane whose source lies
 // outside its row (or whose row the row mask leaves out) gets `old`.  (__shfl_up / __shfl_xor are ds_bpermute: an LDS
 // round trip each, and a scan or a reduction is six of them in a row.)
@@ -157,10 +186,7 @@ __device__ __forceinline__ Tot block_scan_range(Idx n, Load load, Store store, i
 
 // ---- fp64 wave reductions ---------------------------------------------------
 __device__ __forceinline__ double shfl_xor_d(double v, int m) {
-  int lo = __double2loint(v), hi = __double2hiint(v);
-  lo = __shfl_xor(lo, m, 64);
-  hi = __shfl_xor(hi, m, 64);
-  return __hiloint2double(hi, lo);
+  return __longlong_as_double((long long)shfl_xor_u64((unsigned long long)__double_as_longlong(v), m));
 }
 __device__ __forceinline__ double wave_sum_d(double v) {
 #pragma unroll
@@ -188,9 +214,6 @@ __device__ __forceinline__ double max_f64_raw(double a, double b) {
   asm("v_max_f64 %0, %1, %2" : "=v"(r) : "v"(a), "v"(b));
   return r;
 }
-__device__ __forceinline__ double lane63_d(double v) {
-  return __hiloint2double(__builtin_amdgcn_readlane(__double2hiint(v), 63), __builtin_amdgcn_readlane(__double2loint(v), 63));
-}
 __device__ __forceinline__ double wave_min_d(double v) {
   v = min_f64_raw(v, dpp_move_d<0xB1, 0xF>(v));      // quad_perm [1,0,3,2]
   v = min_f64_raw(v, dpp_move_d<0x4E, 0xF>(v));      // quad_perm [2,3,0,1]
@@ -198,7 +221,7 @@ __device__ __forceinline__ double wave_min_d(double v) {
   v = min_f64_raw(v, dpp_move_d<0x140, 0xF>(v));     // row_mirror: every lane of a row holds the row's minimum
   v = min_f64_raw(v, dpp_move_d<0x142, 0xA>(v));     // row_bcast15 into rows 1 and 3
   v = min_f64_raw(v, dpp_move_d<0x143, 0xC>(v));     // row_bcast31 into rows 2 and 3: lane 63 holds the wave's
-  return lane63_d(v);
+  return readlane_d(v, 63);
 }
 __device__ __forceinline__ double wave_max_d(double v) {
   v = max_f64_raw(v, dpp_move_d<0xB1, 0xF>(v));
@@ -207,15 +230,11 @@ __device__ __forceinline__ double wave_max_d(double v) {
   v = max_f64_raw(v, dpp_move_d<0x140, 0xF>(v));
   v = max_f64_raw(v, dpp_move_d<0x142, 0xA>(v));
   v = max_f64_raw(v, dpp_move_d<0x143, 0xC>(v));
-  return lane63_d(v);
+  return readlane_d(v, 63);
 }
 __device__ __forceinline__ unsigned long long wave_sum_u64(unsigned long long v) {
 #pragma unroll
-  for (int m = 32; m >= 1; m >>= 1) {
-    const unsigned int lo = (unsigned int)__shfl_xor((int)(v & 0xFFFFFFFFull), m, 64);
-    const unsigned int hi = (unsigned int)__shfl_xor((int)(v >> 32), m, 64);
-    v += ((unsigned long long)hi << 32) | lo;
-  }
+  for (int m = 32; m >= 1; m >>= 1) v += shfl_xor_u64(v, m);
   return v;
 }
 __device__ __forceinline__ int wave_sum_i(int v) { return wave_sum_i_dpp(v); }
@@ -246,6 +265,36 @@ __device__ __forceinline__ double block_sum_d(double v, double *s_w) {
   return t;
 }
 
+// ---- offset tables -----------------------------------------------------------
+// The largest s in [lo, hi) with off[s] <= key, lo when there is none; among equal offsets (empty segments share one
+// with their successor) the last wins.  PRECONDITION: off[lo + 1 .. hi - 1] are readable -- off[lo] and off[hi] are never
+// read -- and ascending; for a table that is not, the result is unspecified but stays inside [lo, hi).
+template <class Off, class Key>
+__device__ __forceinline__ int last_at_or_below(const Off *off, int lo, int hi, Key key) {
+  while (hi - lo > 1) {
+    const int mid = (lo + hi) >> 1;
+    if (off[mid] <= key) lo = mid; else hi = mid;
+  }
+  return lo;
+}
+// A flat array of rows in scene order, scene b the rows point_off[b] .. point_off[b + 1] - 1 (B + 1 offsets).
+// Rows that belong to a scene: the array may be longer than point_off[B], and a bad table reads nothing outside it.
+__device__ __forceinline__ long long valid_rows(const long long *__restrict__ point_off, int B, long long n_rows) {
+  const long long n = point_off[B];
+  return n < 0 ? 0 : (n < n_rows ? n : n_rows);
+}
+// the offset pair (p0, p1) = point_off[b], point_off[b + 1] describes an array of n_rows rows
+__device__ __forceinline__ bool offsets_ok(long long p0, long long p1, long long n_rows, int b) {
+  return !(p0 > p1 || p0 < 0 || p1 > n_rows || (b == 0 && p0 != 0));
+}
+// The scenes s_lo .. s_hi (both inclusive) that own the rows c0 .. c1 of a chunk; c1 < c0, a chunk beyond the valid rows:
+// s_hi = s_lo.  PRECONDITION: B >= 1 (and last_at_or_below's); both are uniform where c0 and c1 are.
+__device__ __forceinline__ void scenes_of_chunk(const long long *__restrict__ point_off, int B, long long c0, long long c1,
+                                                int &s_lo, int &s_hi) {
+  s_lo = last_at_or_below(point_off, 0, B, c0);
+  s_hi = c1 >= c0 ? last_at_or_below(point_off, s_lo, B, c1) : s_lo;
+}
+
 // ---- calibration arithmetic -------------------------------------------------
 // calibration_kitti.py:104-112, float32: sequential-k FMA chain (== sgemm).
 __device__ __forceinline__ void lidar_to_rect_f32(const float *M, float x, float y,
@@ -274,6 +323,17 @@ __device__ __forceinline__ void rect_to_img_f32(const float *P2, const float r[3
   u = h[0] / r[2];
   v = h[1] / r[2];
   depth = h[2] - P2[2 * 4 + 3];
+}
+// The camera FOV keep rule, get_fov_flag of kitti_dataset.py:140-156 and of vis_utils.py:108-123, float32: the point in
+// the rectified frame, its pixel and depth, then inside the (h, w) image and not behind the camera.  The labels
+// (k_fov_filter) and the training data (k_ing_flag) are both cut by this one statement.  M43, P2: the record's, in
+// registers or in memory.
+__device__ __forceinline__ bool in_image_f32(const float *M43, const float *P2, float x, float y, float z, float h,
+                                             float w) {
+  float r[3], u, v, d;
+  lidar_to_rect_f32(M43, x, y, z, r);
+  rect_to_img_f32(P2, r, u, v, d);
+  return (u >= 0.0f) && (u < w) && (v >= 0.0f) && (v < h) && (d >= 0.0f);
 }
 // a / b for a divisor that is reused many times: r = RN(1/b) is formed once, then
 //   q0 = a*r, rem = fma(-q0, b, a) (exact), q = fma(rem, r, q0)

@@ -35,16 +35,6 @@ __device__ __forceinline__ double max_truncation(int difficulty) {
 struct Combo { int cls, difficulty; double min_overlap; };
 static_assert(sizeof(Combo) == sizeof(dfu3d_eval_combo), "combo");
 
-// frame of flat pair index p: largest f with ov_off[f] <= p
-__device__ __forceinline__ int frame_of(const long long *ov_off, int F, long long p) {
-  int lo = 0, hi = F;
-  while (hi - lo > 1) {
-    const int mid = (lo + hi) >> 1;
-    if (ov_off[mid] <= p) lo = mid; else hi = mid;
-  }
-  return lo;
-}
-
 // eval.py:95-124 for one pair, float64.  crit -1 IoU, 0 / area(a), 1 / area(b)
 __device__ __forceinline__ double image_overlap(const double *a, const double *b, int crit) {
   const double iw = fmin(a[2], b[2]) - fmax(a[0], b[0]);
@@ -68,7 +58,7 @@ __global__ __launch_bounds__(IB) void k_eval_overlaps(int metric, int F, const l
   __shared__ float s_poly[4][MAXV * IB];
   const long long p = (long long)blockIdx.x * IB + threadIdx.x;
   if (p >= n_pairs) return;
-  const int f = frame_of(ov_off, F, p);
+  const int f = last_at_or_below(ov_off, 0, F, p);             // the frame of flat pair index p
   const long long D = dt_off[f + 1] - dt_off[f];
   const long long local = p - ov_off[f];
   const long long i = local / D, j = local - i * D;            // ground truth i, detection j

@@ -17,12 +17,6 @@
 #include "common.hpp"
 
 namespace {
-// a register of lane l, l the same in every lane: v_readlane, not a shuffle through the LDS path (ds_bpermute)
-__device__ __forceinline__ int rl_i(int v, int l) { return __builtin_amdgcn_readlane(v, l); }
-__device__ __forceinline__ double rl_d(double v, int l) {
-  return __hiloint2double(__builtin_amdgcn_readlane(__double2hiint(v), l), __builtin_amdgcn_readlane(__double2loint(v), l));
-}
-
 constexpr int CT = 512;            // threads per clustering workgroup
 constexpr int GRP = 32;            // points per summary / bounding-box group
 constexpr int BLK = 32;            // groups per block (1024 points): second pruning level
@@ -227,7 +221,7 @@ __device__ __forceinline__ void cluster_body(const P par, int *s_summ, float4 *s
       const int pg = in ? par.load(jl) : -3;
       // cheap exit: every query of the wave that still needs this group sits in
       // one set and all 32 points already belong to it (own-chunk groups mostly)
-      const int r_first = rl_i(ri, max(__ffsll((unsigned long long)__ballot(need)) - 1, 0));
+      const int r_first = readlane_i(ri, max(__ffsll((unsigned long long)__ballot(need)) - 1, 0));
       if (__all(!need || ri == r_first) && __all(!in || pg == r_first)) {
         return;
       }
@@ -236,11 +230,11 @@ __device__ __forceinline__ void cluster_body(const P par, int *s_summ, float4 *s
         if ((k & 7) == 7 && k != GRP - 1) {
           // every 8 points: once all queries that need this group have merged into
           // the set that owns all of its points, the rest of the group is moot
-          const int rf = rl_i(ri, max(__ffsll((unsigned long long)__ballot(need)) - 1, 0));
+          const int rf = readlane_i(ri, max(__ffsll((unsigned long long)__ballot(need)) - 1, 0));
           if (__all(!need || ri == rf) && __all(!in || pg == rf)) break;
         }
-        const int pj = rl_i(pg, k);
-        const double xj = rl_d(xg, k), yj = rl_d(yg, k);
+        const int pj = readlane_i(pg, k);
+        const double xj = readlane_d(xg, k), yj = readlane_d(yg, k);
         if (need && (jg + k < i) && pj != ri) {                 // (3) not in my set (yet)
           const double dx = xi - xj, dy = yi - yj;
           const double sq = dx * dx + dy * dy;
@@ -715,7 +709,7 @@ __global__ __launch_bounds__(TCT, (NC <= GRID_NC_SMALL ? 8 : 4)) void k_range_cl
       while (todo) {
         const int src = __ffsll(todo) - 1;
         todo &= todo - 1ull;
-        const int cc = rl_i(c, src), nn = rl_i(nb, src);
+        const int cc = readlane_i(c, src), nn = readlane_i(nb, src);
         if (cell_find(s_par, cc) == cell_find(s_par, nn)) continue;   // merged meanwhile (uniform)
         const int a0 = cc ? s_end[cc - 1] : 0, a1 = s_end[cc];
         const int b0 = s_end[nn - 1], b1 = s_end[nn];
@@ -739,7 +733,7 @@ __global__ __launch_bounds__(TCT, (NC <= GRID_NC_SMALL ? 8 : 4)) void k_range_cl
             while (am) {
               const int k = __ffsll((long long)am) - 1;
               am &= am - 1ull;
-              const double xa = rl_d(xal, k), ya = rl_d(yal, k);
+              const double xa = readlane_d(xal, k), ya = readlane_d(yal, k);
               const double dx = xa - xb, dy = ya - yb;
               const double sq = dx * dx + dy * dy;
               if (vb && sq <= S_HI) {
@@ -1062,7 +1056,7 @@ __global__ __launch_bounds__(FT) void k_fit_gather(
         unsigned long long rem = __ballot(key >= 0);
         while (rem) {
           const int src = __ffsll((long long)rem) - 1;
-          const int k = rl_i(key, src);
+          const int k = readlane_i(key, src);
           const unsigned long long m = __ballot(key == k);
           if (lane == src) s_cnt[wave][k] += __popcll(m);
           rem &= ~m;
@@ -1109,7 +1103,7 @@ __global__ __launch_bounds__(FT) void k_fit_gather(
         unsigned long long rem = __ballot(key >= 0);
         while (rem) {
           const int src = __ffsll((long long)rem) - 1;
-          const int k = rl_i(key, src);
+          const int k = readlane_i(key, src);
           const unsigned long long m = __ballot(key == k);
           const int cur = s_cnt[wave][k];
           if (key == k) {
@@ -1230,7 +1224,7 @@ struct LanePoints {
   double x, y;
   int m;
   template <class F>
-  __device__ __forceinline__ void each(F f) const { for (int j = 0; j < m; j++) f(rl_d(x, j), rl_d(y, j)); }
+  __device__ __forceinline__ void each(F f) const { for (int j = 0; j < m; j++) f(readlane_d(x, j), readlane_d(y, j)); }
   __device__ __forceinline__ void reduce(Extent &) const {}
   __device__ __forceinline__ double sum(double v) const { return v; }
   __device__ __forceinline__ int sum(int v) const { return v; }

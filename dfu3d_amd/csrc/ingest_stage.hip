@@ -12,8 +12,9 @@
 //                chunk that holds row point_off[b] plus the flags of that chunk in front of the row.
 //   k_ing_write  the flags again, a block rank, the kept rows to their place: all C columns, bit for bit.
 //   k_ing_boxes  one workgroup per box: the kept rows of the box's scene through pt_in_box, one workgroup sum.
-// The flat array is in scene order, so the one stable compaction is the scenes' concatenation.  The arithmetic of the
-// keep rule is common.hpp's and of the box rule pt_in_box.hpp's: nothing of either is restated here.
+// The flat array is in scene order, so the one stable compaction is the scenes' concatenation.  The keep rule -- its
+// arithmetic and its five comparisons, in_image_f32 -- and the search of a row's scene are common.hpp's, the box rule is
+// pt_in_box.hpp's: nothing of them is restated here.
 #include "common.hpp"
 #include "dfu3d_ingest.h"
 #include "pt_in_box.hpp"
@@ -23,29 +24,6 @@ namespace {
 constexpr int PT = DFU3D_ING_CHUNK;                 // threads per workgroup = rows per chunk
 constexpr int NW = PT / 64;
 static_assert(PT == 4 * 64, "chunk: k_ing_scan reads a chunk's flags as one word per lane of one wave");
-
-// the last b in [lo, hi] with off[b] <= row (empty scenes share an offset with their successor: the last wins)
-template <class T>
-__device__ __forceinline__ int owner_of(const T *__restrict__ off, int lo, int hi, long long row) {
-  while (lo < hi) {
-    const int mid = (lo + hi + 1) >> 1;
-    if ((long long)off[mid] <= row) lo = mid; else hi = mid - 1;
-  }
-  return lo;
-}
-
-// rows that belong to a scene: the array may be longer than point_off[B]
-__device__ __forceinline__ long long valid_rows(const long long *__restrict__ point_off, int B, long long n_rows) {
-  const long long n = point_off[B];
-  return n < 0 ? 0 : (n < n_rows ? n : n_rows);
-}
-
-__device__ __forceinline__ bool keep_rule(const ViewCalib *__restrict__ c, float x, float y, float z, float h, float w) {
-  float r[3], u, v, d;
-  lidar_to_rect_f32(c->M43, x, y, z, r);
-  rect_to_img_f32(c->P2, r, u, v, d);
-  return (u >= 0.0f) && (u < w) && (v >= 0.0f) && (v < h) && (d >= 0.0f);
-}
 
 __global__ __launch_bounds__(PT) void k_ing_flag(const float *__restrict__ pts, long long n_rows, int C, bool vec4,
                                                  const long long *__restrict__ point_off, int B,
@@ -59,7 +37,7 @@ __global__ __launch_bounds__(PT) void k_ing_flag(const float *__restrict__ pts, 
     uint32_t bad = 0u;
     for (int b = threadIdx.x; b < B; b += PT) {
       const long long p0 = point_off[b], p1 = point_off[b + 1];
-      if (p0 > p1 || p0 < 0 || p1 > n_rows || (b == 0 && p0 != 0)) bad |= (uint32_t)DFU3D_ING_ST_OFFSETS;
+      if (!offsets_ok(p0, p1, n_rows, b)) bad |= (uint32_t)DFU3D_ING_ST_OFFSETS;
       const int h = shape[2 * b], w = shape[2 * b + 1];
       if (h < 0 || w < 0 || h > DFU3D_ING_MAX_SIDE || w > DFU3D_ING_MAX_SIDE) bad |= (uint32_t)DFU3D_ING_ST_SHAPE;
       if (with_boxes) {
@@ -72,12 +50,12 @@ __global__ __launch_bounds__(PT) void k_ing_flag(const float *__restrict__ pts, 
   }
   const long long c0 = (long long)blockIdx.x * PT;
   const long long c1 = (c0 + PT < n_valid ? c0 + PT : n_valid) - 1;
-  const int s_lo = owner_of(point_off, 0, B - 1, c0);                      // uniform over the workgroup
-  const int s_hi = c1 >= c0 ? owner_of(point_off, s_lo, B - 1, c1) : s_lo;
+  int s_lo, s_hi;                                    // uniform over the workgroup
+  scenes_of_chunk(point_off, B, c0, c1, s_lo, s_hi);
   const long long i = c0 + threadIdx.x;
   bool k = false;
   if (i < n_valid) {
-    const int s = (s_lo == s_hi) ? s_lo : owner_of(point_off, s_lo, s_hi, i);
+    const int s = (s_lo == s_hi) ? s_lo : last_at_or_below(point_off, s_lo, s_hi + 1, i);
     const int h = shape[2 * s], w = shape[2 * s + 1];
     float x, y, z;
     if (vec4) {                                        // uniform: C = 4 and both arrays 16-byte aligned
@@ -88,7 +66,7 @@ __global__ __launch_bounds__(PT) void k_ing_flag(const float *__restrict__ pts, 
       x = q[0]; y = q[1]; z = q[2];
     }
     const bool shape_ok = h >= 0 && w >= 0 && h <= DFU3D_ING_MAX_SIDE && w <= DFU3D_ING_MAX_SIDE;
-    k = shape_ok && i >= point_off[s] && keep_rule(calib + s, x, y, z, (float)h, (float)w);
+    k = shape_ok && i >= point_off[s] && in_image_f32(calib[s].M43, calib[s].P2, x, y, z, (float)h, (float)w);
   }
   if (i < n_rows) keep[i] = k ? 1 : 0;
   const int tot = block_sum_i<NW>(k ? 1 : 0, s_w);
@@ -149,7 +127,7 @@ __global__ __launch_bounds__(PT) void k_ing_boxes(const float *__restrict__ pts,
                                                   int *__restrict__ box_cnt) {
   __shared__ int s_w[NW];
   const int kb = blockIdx.x;
-  const int s = owner_of(box_off, 0, B - 1, kb);     // uniform
+  const int s = last_at_or_below(box_off, 0, B, kb);     // uniform
   const bool owned = box_off[s] <= kb && kb < box_off[s + 1];
   const long long n_valid = valid_rows(point_off, B, n_rows);
   long long p0 = point_off[s], p1 = point_off[s + 1];

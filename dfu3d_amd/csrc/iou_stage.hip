@@ -95,9 +95,7 @@ __global__ __launch_bounds__(64) void k_nms_reduce(int n, const unsigned long lo
 #pragma unroll
     for (int w = 0; w < MAXW; w++)
       if (w == (nblock >> 6)) word = remv[w];
-    const unsigned lo = __shfl((unsigned)(word & 0xFFFFFFFFull), nblock & 63, 64);
-    const unsigned hi = __shfl((unsigned)(word >> 32), nblock & 63, 64);
-    word = ((unsigned long long)hi << 32) | lo;
+    word = shfl_u64(word, nblock & 63);
     if (!(word & (1ULL << inblock))) {
       if (lane == 0) keep[nk] = i;
       nk++;

@@ -47,10 +47,7 @@ __global__ __launch_bounds__(NT) void k_fov_filter(
       bool ok = false;
       if (i < n) {
         const float4 p = pts[p0 + i];
-        float r[3], u, w, d;
-        lidar_to_rect_f32(c.M43, p.x, p.y, p.z, r);
-        rect_to_img_f32(c.P2, r, u, w, d);
-        ok = (u >= 0.0f) && (u < fovW) && (w >= 0.0f) && (w < fovH) && (d >= 0.0f);
+        ok = in_image_f32(c.M43, c.P2, p.x, p.y, p.z, fovH, fovW);
       }
       flags[k] = __ballot(ok);
       mine += __popcll(flags[k]);

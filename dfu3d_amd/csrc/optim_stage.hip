@@ -74,10 +74,6 @@ __global__ __launch_bounds__(OT) void k_opt_sumsq(const dfu3d_opt_tensor *__rest
   if (threadIdx.x == 0) partial[blockIdx.x] = acc;
 }
 
-__device__ __forceinline__ double readlane_d(double v, int k) {
-  return __hiloint2double(__builtin_amdgcn_readlane(__double2hiint(v), k), __builtin_amdgcn_readlane(__double2loint(v), k));
-}
-
 __global__ __launch_bounds__(64) void k_opt_total(const double *__restrict__ partial, int n_chunks, double max_norm,
                                                   double *__restrict__ out_norm, uint32_t *__restrict__ status) {
   const int lane = threadIdx.x;

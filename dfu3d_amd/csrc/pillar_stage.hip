@@ -174,10 +174,6 @@ __global__ __launch_bounds__(PT) void k_pv_sort(const int *__restrict__ sizes, c
   plist[s + rank] = e;
 }
 
-__device__ __forceinline__ float lane_f(float v, int lane) {
-  return __int_as_float(__builtin_amdgcn_readlane(__float_as_int(v), lane));
-}
-
 // Mean of every pillar: one wave walks the CSR range of PW consecutive pillars, 64 rows per step gathered by the lanes
 // (the next step's rows are requested before this step's are added), and adds them one after the other in list order.
 __global__ __launch_bounds__(64) void k_pv_mean(const float *__restrict__ pts, int cols, const int *__restrict__ kept_idx,
@@ -215,9 +211,9 @@ __global__ __launch_bounds__(64) void k_pv_mean(const float *__restrict__ pts, i
         cur_end = offsets[cur + 1];
         sx = sy = sz = 0.0f;
       }
-      sx += lane_f(x, j);
-      sy += lane_f(y, j);
-      sz += lane_f(z, j);
+      sx += readlane_f(x, j);
+      sy += readlane_f(y, j);
+      sz += readlane_f(z, j);
     }
   }
   if (lane == 0) {

@@ -1211,7 +1211,7 @@ __device__ __forceinline__ void ph_ovf_select(int v, int bx, int gx,
   }
 #pragma unroll
   for (int x = 32; x >= 1; x >>= 1) {
-    const unsigned long long o = __shfl_xor(m, x, 64);
+    const unsigned long long o = shfl_xor_u64(m, x);
     m = o < m ? o : m;
   }
   if (lane_id() == 0) s_min[threadIdx.x >> 6] = m;

@@ -40,9 +40,6 @@ __device__ __forceinline__ float sqdist(float ax, float ay, float az, float bx, 
   return (ax - bx) * (ax - bx) + (ay - by) * (ay - by) + (az - bz) * (az - bz);
 }
 __device__ __forceinline__ int wave_max_i(int v) { return ~wave_min_i_dpp(~v); }
-__device__ __forceinline__ float readlane_f(float v, int l) {
-  return __int_as_float(__builtin_amdgcn_readlane(__float_as_int(v), l));
-}
 __device__ __forceinline__ void status_or(uint32_t st, uint32_t *__restrict__ status) {   // all lanes of the wave call it
   st = wave_or_u32_dpp(st);
   if (lane_id() == 0 && st) atomicOr(status, st);

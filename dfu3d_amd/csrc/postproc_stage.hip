@@ -73,19 +73,6 @@ __global__ __launch_bounds__(IB) void k_pp_mask(const float *__restrict__ boxes,
   }
 }
 
-// lane l's 64-bit value, l wave-uniform
-__device__ __forceinline__ unsigned long long read_lane64(unsigned long long v, int l) {
-  const unsigned lo = __builtin_amdgcn_readlane((unsigned)(v & 0xFFFFFFFFull), l);
-  const unsigned hi = __builtin_amdgcn_readlane((unsigned)(v >> 32), l);
-  return ((unsigned long long)hi << 32) | lo;
-}
-
-__device__ __forceinline__ unsigned long long or_xor64(unsigned long long v, int m) {
-  const unsigned lo = __shfl_xor((unsigned)(v & 0xFFFFFFFFull), m, 64);
-  const unsigned hi = __shfl_xor((unsigned)(v >> 32), m, 64);
-  return v | (((unsigned long long)hi << 32) | lo);
-}
-
 __global__ __launch_bounds__(PT) void k_pp_walk(const unsigned long long *__restrict__ mask,
                                                 const int *__restrict__ count, int cap, int wcap, int pre_max,
                                                 int post_max, int *__restrict__ keep, int *__restrict__ num_keep) {
@@ -113,14 +100,14 @@ __global__ __launch_bounds__(PT) void k_pp_walk(const unsigned long long *__rest
       const int r0 = blk * 64;
       unsigned long long diag = 0ull;
       if (r0 + lane < n) diag = staged ? s_rows[(r0 + lane) * wn + blk] : g[(size_t)(r0 + lane) * wcap + blk];
-      unsigned long long cur = read_lane64(remv, blk);      // bit set: suppressed, walked or beyond the segment
+      unsigned long long cur = readlane_u64(remv, blk);      // bit set: suppressed, walked or beyond the segment
       if (n - r0 < 64) cur |= ~0ull << (n - r0);
       unsigned long long kept = 0ull;
       while (~cur != 0ull && nk < limit) {
         const int b = __ffsll((long long)~cur) - 1;
         kept |= 1ull << b;
         nk++;
-        cur |= read_lane64(diag, b) | (1ull << b);
+        cur |= readlane_u64(diag, b) | (1ull << b);
       }
       if (lane == 0) s_kept[blk] = kept;
       if (blk + 1 < wn) {
@@ -132,8 +119,8 @@ __global__ __launch_bounds__(PT) void k_pp_walk(const unsigned long long *__rest
           if (mine && ((kept >> r) & 1ull))
             acc |= staged ? s_rows[(r0 + r) * wn + w] : g[(size_t)(r0 + r) * wcap + w];
         }
-        acc = or_xor64(acc, 16);
-        acc = or_xor64(acc, 32);
+        acc |= shfl_xor_u64(acc, 16);
+        acc |= shfl_xor_u64(acc, 32);
         remv |= acc;
       }
     }

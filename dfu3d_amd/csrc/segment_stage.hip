@@ -233,9 +233,8 @@ __global__ __launch_bounds__(SEG_WPB * 64) void k_seg_write(
         const bool has = (b[k] >> j) & 1u;
         const unsigned long long m = __ballot(has);
         // (j is the same in every lane: a read of lane j, not a shuffle through the LDS path)
-        const long long start = (long long)(((unsigned long long)(uint32_t)__builtin_amdgcn_readlane((int)(woff >> 32), j) << 32) |
-                                            (uint32_t)__builtin_amdgcn_readlane((int)(woff & 0xFFFFFFFFll), j));
-        const uint32_t swj = (uint32_t)__builtin_amdgcn_readlane((int)sw, j);
+        const long long start = (long long)readlane_u64((unsigned long long)woff, j);
+        const uint32_t swj = (uint32_t)readlane_i((int)sw, j);
         if (has) {
           const long long d = start + __popcll(m & ((1ull << lane) - 1ull));
           px[d] = x[k];
@@ -263,16 +262,6 @@ __device__ __forceinline__ void tile_scan(int S, F tiles, int *__restrict__ tile
 __global__ __launch_bounds__(1024) void k_tile_scan(int S, const int *__restrict__ cnt,
                                                     int *__restrict__ tile_off, int qt) {
   tile_scan(S, [&](int s) { return (cnt[s] + qt - 1) / qt; }, tile_off);
-}
-
-// largest s with tile_off[s] <= t  (t < tile_off[S])
-__device__ __forceinline__ int find_segment(const int *tile_off, int S, int t) {
-  int lo = 0, hi = S;
-  while (hi - lo > 1) {
-    const int mid = (lo + hi) >> 1;
-    if (tile_off[mid] <= t) lo = mid; else hi = mid;
-  }
-  return lo;
 }
 
 // ---------------------------------------------------------------- a10 radius
@@ -531,9 +520,7 @@ __global__ __launch_bounds__(RFB, NB1 ? RF_OCC : RF_OCC - 1) void k_rf_stream(
         if (__ballot(active && cnt <= nb)) {
           const int l1 = rf_nbr_lane(lane, RF_ND1), l2 = rf_nbr_lane(lane, RF_ND2);
           for (int j = 0; j < 64; j += RF_STRIDE) {
-            const float xj = __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, x), j));
-            const float yj = __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, y), j));
-            const float zj = __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, z), j));
+            const float xj = readlane_f(x, j), yj = readlane_f(y, j), zj = readlane_f(z, j);
             const uint32_t wj = (uint32_t)__builtin_amdgcn_readlane((int)wb, j);
             const float dx = x - xj, dy = y - yj, dz = z - zj;
             if (wj == wb && dx * dx + dy * dy + dz * dz < thr2 && j != lane && j != l1 && j != l2) cnt++;
@@ -999,7 +986,7 @@ __global__ __launch_bounds__(QT) void k_shadow_build(
     const double *__restrict__ radius, int S, const int *__restrict__ tile_off, float4 *__restrict__ pq) {
   const int ntile = tile_off[S];
   for (int t = blockIdx.x; t < ntile; t += gridDim.x) {
-    const int s = find_segment(tile_off, S, t);
+    const int s = last_at_or_below(tile_off, 0, S, t);
     const int q = (t - tile_off[s]) * QT + threadIdx.x;
     if (q >= seg_cnt[s]) continue;
     const long long i = seg_base[s] + q;
@@ -1071,7 +1058,7 @@ __global__ __launch_bounds__(BT) void k_ball_flags(
   int t = blockIdx.x * BALL_TPW;
   if (t >= ntile) return;
   const int t_end = min(t + BALL_TPW, ntile);
-  int s = find_segment(tile_off, S, t);
+  int s = last_at_or_below(tile_off, 0, S, t);
   const double inv = 16.0 / (C * (1.0 + 1e-5));  // quantisation: 16 units per C
   const double Cq = C * (1.0 + 1e-6);
   const double OFF = 65536.0;                    // quantised coordinates are stored with this offset
@@ -1478,7 +1465,7 @@ __global__ __launch_bounds__(KQ) void k_knn_mean(
   extern __shared__ double s_best[];            // knn x KQ
   const int t = blockIdx.x;
   if (t >= tile_off[S]) return;
-  const int s = find_segment(tile_off, S, t);
+  const int s = last_at_or_below(tile_off, 0, S, t);
   if (!enable[s]) return;
   const int q0 = (t - tile_off[s]) * KQ;
   const int n = seg_cnt[s];

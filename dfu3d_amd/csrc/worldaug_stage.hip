@@ -52,15 +52,6 @@ __device__ __forceinline__ bool in_range_xy(const float *__restrict__ range, flo
   return x >= range[0] && x <= range[3] && y >= range[1] && y <= range[4];
 }
 
-// the last scene b in [lo, hi] with point_off[b] <= row (empty scenes share an offset with their successor: the last wins)
-__device__ __forceinline__ int scene_of(const long long *__restrict__ point_off, int lo, int hi, long long row) {
-  while (lo < hi) {
-    const int mid = (lo + hi + 1) >> 1;
-    if (point_off[mid] <= row) lo = mid; else hi = mid - 1;
-  }
-  return lo;
-}
-
 template <class T> struct BoxK;
 template <> struct BoxK<float> {
   static __device__ __forceinline__ float pi() { return 3.14159274101257324f; }
@@ -133,8 +124,7 @@ __global__ __launch_bounds__(PT) void k_wa_boxes(const T *__restrict__ boxes, in
   if (t == 0) {
     point_cnt[b] = 0;
     const long long p0 = point_off[b], p1 = point_off[b + 1];
-    if (p0 > p1 || p0 < 0 || p1 > n_rows || (b == 0 && p0 != 0))
-      atomicOr(status, (uint32_t)DFU3D_AUG_ST_OFFSETS);
+    if (!offsets_ok(p0, p1, n_rows, b)) atomicOr(status, (uint32_t)DFU3D_AUG_ST_OFFSETS);
   }
   if (r0 < 0 || n < 0 || r0 + n > n_box_rows || (long long)n > (long long)box_off[b + 1] - r0) {
     if (t == 0) atomicOr(status, (uint32_t)DFU3D_AUG_ST_OFFSETS);
@@ -200,12 +190,10 @@ __device__ __forceinline__ int rows_of(const float *__restrict__ pts, long long 
                                        const dfu3d_aug_params *__restrict__ params, const float *__restrict__ range,
                                        int mode, long long chunk, RowSet &R, bool &nonfinite, int &s_lo, int &s_hi) {
   // the array may be longer than the scenes it holds (a capacity): rows at or beyond point_off[B] are never read
-  long long n_valid = point_off[B];
-  n_valid = n_valid < 0 ? 0 : (n_valid < n_rows ? n_valid : n_rows);
+  const long long n_valid = valid_rows(point_off, B, n_rows);
   const long long c0 = chunk * DFU3D_AUG_CHUNK;
   const long long c1 = (c0 + DFU3D_AUG_CHUNK < n_valid ? c0 + DFU3D_AUG_CHUNK : n_valid) - 1;
-  s_lo = scene_of(point_off, 0, B - 1, c0);          // uniform over the workgroup
-  s_hi = c1 >= c0 ? scene_of(point_off, s_lo, B - 1, c1) : s_lo;
+  scenes_of_chunk(point_off, B, c0, c1, s_lo, s_hi);   // uniform over the workgroup
   const long long i0 = c0 + (long long)threadIdx.x * PE;
   int mine = 0;
   nonfinite = false;
@@ -215,7 +203,7 @@ __device__ __forceinline__ int rows_of(const float *__restrict__ pts, long long 
     R.sc[k] = s_lo;
     R.x[k] = R.y[k] = R.z[k] = 0.0f;
     if (i0 + k < n_valid) {
-      const int s = (s_lo == s_hi) ? s_lo : scene_of(point_off, s_lo, s_hi, i0 + k);
+      const int s = (s_lo == s_hi) ? s_lo : last_at_or_below(point_off, s_lo, s_hi + 1, i0 + k);
       const float *q = pts + (size_t)(i0 + k) * C;
       float x = q[0], y = q[1], z = WITH_Z ? q[2] : 0.0f;
       xf_point(params[s], x, y, z);

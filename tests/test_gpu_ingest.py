@@ -83,6 +83,11 @@ def test_sizes_around_the_wave_and_the_chunk(C):
     # and each of them alone
     for b, n in enumerate(sizes):
         _check([_cloud(rng, n, C)], _calibs(1), [SHAPES[b % 2]])
+    # two empty scenes side by side inside one chunk and an empty last scene, in the rows and in the box table
+    sizes = (70, 0, 0, 130, 0)
+    flags, cnt = _check([_cloud(rng, n, C) for n in sizes], _calibs(len(sizes)), [SHAPES[b % 2] for b in range(len(sizes))],
+                        [_boxes_for(rng, m) for m in (2, 0, 0, 3, 0)])
+    assert flags[0].any() and flags[3].any() and len(cnt) == 5
 
 
 def test_a_scan_that_carries_across_more_than_1024_chunks():

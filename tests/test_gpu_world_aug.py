@@ -96,6 +96,11 @@ def test_one_batch_of_all_scenes_equals_the_restatement_and_the_golden(ci):
         assert off[s + 1] - off[s] == keep.sum()                                           # the reference's decisions
         if len(p) >= 64 or W.planted(ci, s):
             assert W.same_bits(out[off[s]:off[s + 1], 1:4], G['aug/%d/%d/xyz' % (ci, s)][keep])
+    # two empty scenes side by side inside one chunk and an empty last scene (scene 0 is the empty one)
+    ops = _ops(ci, [2, 0, 0, 3, 8, 0])
+    want = R.batch(ops, W.pc_range(ci), mask_boxes=W.training(ci))
+    assert len(want[0]) > 0
+    _check_against_restatement(_run(ops, W.pc_range(ci), W.training(ci)), want, sum(len(o[0]) for o in ops))
 
 
 def test_rows_beyond_the_last_offset_are_never_read():
