@@ -13,7 +13,8 @@
 // non-negative floats, for which the integer order is the float order, and max does not depend on the order of the draws.
 //
 // dfu3d_center_decode = decode_bbox_from_heatmap (centernet_utils.py:155-241), k_cd_decode, one workgroup per sample.
-// Radix select over the 32 score bits (four 8-bit passes with an LDS histogram) finds the K-th largest score T; one more
+// The workgroup radix select of common.hpp (block_select, the one the plane medians and the repair use) over the
+// complemented 32 score bits at rank K - 1 finds the K-th largest score T and how many ties at T are kept; one more
 // pass collects the scores above T in any order and, by an ordered block scan, the first ties at T by ascending flat index.
 // The candidates are sorted in LDS as 64-bit keys (score bits, ~flat index): descending score, ties by ascending index,
 // NaN first.  Every thread then gathers and decodes one row, and a block scan compacts the rows that pass the range and
@@ -200,18 +201,6 @@ __device__ __forceinline__ uint32_t score_key(float v) {
   return (b & 0x80000000u) ? ~b : (b | 0x80000000u);
 }
 
-// s_hist[d] += 1 for the active lanes; the lanes that share the first active lane's digit add once (a map of equal
-// scores would otherwise serialise the whole wave on one LDS word)
-__device__ __forceinline__ void hist_add(int *s_hist, bool act, int d) {
-  const unsigned long long m = __ballot(act);
-  if (!m) return;
-  const int leader = __ffsll((long long)m) - 1;
-  const int d0 = __shfl(d, leader, 64);
-  const unsigned long long same = __ballot(act && d == d0);
-  if (lane_id() == leader) atomicAdd(&s_hist[d0], __popcll(same));
-  else if (act && d != d0) atomicAdd(&s_hist[d], 1);
-}
-
 __global__ __launch_bounds__(DT) void k_cd_decode(const float *__restrict__ heat, const float *__restrict__ rot_cos,
                                                   const float *__restrict__ rot_sin, const float *__restrict__ center,
                                                   const float *__restrict__ center_z, const float *__restrict__ dim,
@@ -222,43 +211,17 @@ __global__ __launch_bounds__(DT) void k_cd_decode(const float *__restrict__ heat
   __shared__ unsigned long long s_key[DK];
   __shared__ int s_hist[256];
   __shared__ int s_w[DT / 64];
-  __shared__ int s_sel[2];
+  __shared__ unsigned long long s_sel[3];
   __shared__ int s_cnt;
   const int b = blockIdx.x, t = threadIdx.x;
   const int HW = g.H * g.W, N = g.n_cls * HW, K = g.K;
   const float *hp = heat + (size_t)b * N;
 
-  // the K-th largest key: most significant digit first
-  uint32_t prefix = 0u, pmask = 0u;
-  int krem = K;
-  for (int shift = 24; shift >= 0; shift -= 8) {
-    if (t < 256) s_hist[t] = 0;
-    __syncthreads();
-    for (int i0 = 0; i0 < N; i0 += DT) {
-      const int i = i0 + t;
-      const uint32_t key = i < N ? score_key(hp[i]) : 0u;
-      hist_add(s_hist, i < N && (key & pmask) == prefix, (int)((key >> shift) & 255u));
-    }
-    __syncthreads();
-    if (t == 0) {
-      int cum = 0, d = 255;
-      for (; d > 0; d--) {
-        const int c = s_hist[d];
-        if (cum + c >= krem) break;
-        cum += c;
-      }
-      s_sel[0] = d;
-      s_sel[1] = cum;
-    }
-    __syncthreads();
-    prefix |= (uint32_t)s_sel[0] << shift;
-    pmask |= 255u << shift;
-    krem -= s_sel[1];
-    __syncthreads();
-  }
+  // the K-th largest key is the complement of the key with ascending rank K - 1 among the complements (K <= N: host check)
+  const auto sel = block_select<DT, 32, uint32_t>(N, K - 1, [&](int i) { return ~score_key(hp[i]); }, s_hist, s_sel);
   // keys above T in any order into [0, G), the first `need` keys equal to T by ascending index into [G, K)
-  const uint32_t T = prefix;
-  const int need = krem, G = K - need;
+  const uint32_t T = ~sel.key;
+  const int need = sel.rank + 1, G = K - need;
   if (t == 0) s_cnt = 0;
   for (int i = t; i < DK; i += DT) s_key[i] = 0ull;      // padding sorts last: no real key is 0
   __syncthreads();

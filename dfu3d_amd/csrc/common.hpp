@@ -184,6 +184,88 @@ __device__ __forceinline__ Tot block_scan_range(Idx n, Load load, Store store, i
   return carry;
 }
 
+// ---- workgroup radix select ---------------------------------------------------
+// One histogram increment per lane with active set, for a wave whose keys crowd into few buckets (the high bytes
+// of a view's heights do: thousands of equal sign/exponent bytes; a constant heat map puts every key into one): up to
+// four rounds in which the first remaining lane's bucket is counted by ballot and added once, plain LDS atomics for
+// what is left.  Same-address LDS atomics serialise lane by lane; this was most of k_plane_ransac's time.
+// PRECONDITION: wave-uniform control flow (ballots).
+__device__ __forceinline__ void hist_add_wave(int *hist, bool active, int bucket) {
+  unsigned long long rem = __ballot(active);
+  const int lane = lane_id();
+  for (int r = 0; r < 4 && rem; r++) {                      // uniform
+    const int leader = __ffsll((long long)rem) - 1;
+    const int lb = __shfl(bucket, leader, 64);
+    const bool same = active && bucket == lb;
+    const unsigned long long sm = __ballot(same);
+    if (lane == leader) atomicAdd(&hist[lb], __popcll(sm));
+    rem &= ~sm;
+    if (same) active = false;
+  }
+  if (active) atomicAdd(&hist[bucket], 1);
+}
+
+// The key with 0-based ascending rank k among the n keys keyfn(0), ..., keyfn(n - 1), by ONE workgroup of NT threads:
+// 8-bit radix passes from bit BITS - 8 down over keys of type Key that fit BITS bits, in every thread.  `rank`: the
+// 0-based rank of the selected element among the keys EQUAL to the returned one (0 when it is the only one).  Leaves
+// as soon as the bucket that holds the rank has a single key in it (one more sweep fetches that key).
+// PRECONDITION: ALL threads of the workgroup call it from uniform control flow with the same n and k, 0 <= k < n, and
+// NT is a multiple of 64.  hist: 256 ints of LDS, s_sel: 3 x u64 of LDS.  On return hist holds the bucket counts of
+// the last pass made and s_sel the last hand-off (s_sel[0] the returned key); every thread is past the last barrier, so
+// both are reusable at once.
+template <class Key> struct Selected { Key key; int rank; };
+template <int NT, int BITS, class Key, class KeyFn>
+__device__ Selected<Key> block_select(int n, int k, KeyFn keyfn, int *hist, unsigned long long *s_sel) {
+  static_assert(NT % 64 == 0 && BITS % 8 == 0 && BITS <= 8 * (int)sizeof(Key), "block_select");
+  Key prefix = 0, mask = 0;
+  int kk = k;
+  for (int shift = BITS - 8; shift >= 0; shift -= 8) {
+    for (int b = threadIdx.x; b < 256; b += NT) hist[b] = 0;
+    __syncthreads();
+    for (int base = 0; base < n; base += NT) {              // uniform trip count: ballots inside
+      const int i = base + threadIdx.x;
+      Key key = 0;
+      bool act = false;
+      if (i < n) { key = keyfn(i); act = (key & mask) == prefix; }
+      hist_add_wave(hist, act, (int)((key >> shift) & (Key)0xFF));
+    }
+    __syncthreads();
+    if (threadIdx.x < 64) {       // the bucket that holds rank kk: one wave, four buckets per lane
+      const int l = threadIdx.x;
+      const int c0 = hist[4 * l], c1 = hist[4 * l + 1], c2 = hist[4 * l + 2], c3 = hist[4 * l + 3];
+      const int inc = wave_incl_scan(c0 + c1 + c2 + c3);
+      const unsigned long long past = __ballot(inc > kk);     // lanes whose running total passes kk
+      const int tl = past ? (__ffsll((long long)past) - 1) : 63;   // (past == 0 cannot happen for k < n)
+      if (l == tl) {
+        int acc = inc - (c0 + c1 + c2 + c3), b = 4 * l, cb = c0;
+        if (acc + c0 <= kk) { acc += c0; b++; cb = c1;
+          if (acc + c1 <= kk) { acc += c1; b++; cb = c2;
+            if (acc + c2 <= kk) { acc += c2; b++; cb = c3; } } }
+        s_sel[0] = prefix | ((Key)b << shift);
+        s_sel[1] = (unsigned long long)(kk - acc);
+        s_sel[2] = (unsigned long long)cb;
+      }
+    }
+    __syncthreads();
+    prefix = (Key)s_sel[0];
+    kk = (int)s_sel[1];
+    const int in_bucket = (int)s_sel[2];
+    mask |= ((Key)0xFF << shift);
+    __syncthreads();
+    if (in_bucket == 1 && shift > 0) {                      // (uniform) exactly one key carries this prefix
+      for (int i = threadIdx.x; i < n; i += NT) {
+        const Key key = keyfn(i);
+        if ((key & mask) == prefix) s_sel[0] = key;
+      }
+      __syncthreads();
+      prefix = (Key)s_sel[0];
+      __syncthreads();
+      return {prefix, 0};
+    }
+  }
+  return {prefix, kk};
+}
+
 // ---- fp64 wave reductions ---------------------------------------------------
 __device__ __forceinline__ double shfl_xor_d(double v, int m) {
   return __longlong_as_double((long long)shfl_xor_u64((unsigned long long)__double_as_longlong(v), m));

@@ -1160,7 +1160,7 @@ __device__ __forceinline__ void ph_ovf_select(int v, int bx, int gx,
     int cap_ovf, const uint32_t *__restrict__ ovf_bins, const int *__restrict__ n_ovf,
     const int *__restrict__ ovf_cnt, const uint32_t *__restrict__ ovf_list) {
   __shared__ int hist[256];
-  __shared__ uint32_t s_sel[2];
+  __shared__ unsigned long long s_sel[3];
   __shared__ unsigned long long s_min[4];
   const int no = min(n_ovf[v], cap_ovf);
   const Table T = table_view(table, E_total);
@@ -1171,35 +1171,10 @@ __device__ __forceinline__ void ph_ovf_select(int v, int bx, int gx,
   const int n = ovf_cnt[(size_t)v * cap_ovf + s];
   const uint32_t *lst = ovf_list + (size_t)v * HW + T.rep[e];
   __syncthreads();
-  // radix select (24 bits, 3 x 8) of the value with 0-based rank max_points-1
-  uint32_t prefix = 0u, mask = 0u;
-  int kk = max_points - 1;
-  for (int shift = 16; shift >= 0; shift -= 8) {
-    hist[threadIdx.x] = 0;
-    __syncthreads();
-    for (int i = threadIdx.x; i < n; i += 256) {
-      const uint32_t key = lst[i];
-      if ((key & mask) == prefix) atomicAdd(&hist[(key >> shift) & 0xFFu], 1);
-    }
-    __syncthreads();
-    if (threadIdx.x == 0) {
-      int acc = 0, b = 0;
-      for (; b < 256; b++) {
-        const int c = hist[b];
-        if (acc + c > kk) break;
-        acc += c;
-      }
-      if (b > 255) b = 255;
-      s_sel[0] = prefix | ((uint32_t)b << shift);
-      s_sel[1] = (uint32_t)(kk - acc);
-    }
-    __syncthreads();
-    prefix = s_sel[0];
-    kk = (int)s_sel[1];
-    mask |= (0xFFu << shift);
-    __syncthreads();
-  }
-  const uint32_t thr = prefix;
+  // the max_points-th smallest pixel of the list, or its largest: a bin queued for two colliding keys is no longer than the
+  // cap and keeps every pixel (block_select wants rank < n)
+  const uint32_t thr =
+      block_select<256, 24, uint32_t>(n, min(n, max_points) - 1, [&](int i) { return lst[i]; }, hist, s_sel).key;
   unsigned long long m = ~0ull;
   for (int i = threadIdx.x; i < n; i += 256) {
     const uint32_t pix = lst[i];
@@ -1569,7 +1544,7 @@ static int backproject_bin_impl(
   if (max_inst > DFU3D_MAX_INST) return DFU3D_ERANGE;
   if (masks && !mask_format_ok(mask_format, max_inst)) return DFU3D_EINVAL;
   const int64_t HW64 = (int64_t)H * W;
-  if (HW64 >= (1ll << 24)) return DFU3D_ERANGE;     // 24-bit pixel radix select
+  if (HW64 >= (1ll << 24)) return DFU3D_ERANGE;     // ph_ovf_select: block_select with BITS = 24 over the pixels
   if (W % 4) return DFU3D_EINVAL;                    // float4 row loads
   if (geom->max_points_per_voxel < 1) return DFU3D_EINVAL;
   if (((uintptr_t)blk_cnt & 7u) != 0) return DFU3D_EINVAL;   // 64-bit counters in front

@@ -256,6 +256,45 @@ def test_decode_ties_by_ascending_flat_index():
         assert len(ties) >= 40 and (flat[1:][ties] < flat[1:][ties + 1]).all()
 
 
+def _select_case(name):
+    """-> (heat maps (2, n_cls, H, W), K): inputs that steer the radix select behind the K-th largest score."""
+    n_cls, H, W, K = {'k_equals_n': (1, 8, 8, 64), 'nan_first': (2, 9, 7, 1), 'alone_in_top_byte': (1, 33, 31, 1),
+                      'last_byte_only': (1, 16, 16, 100), 'constant': (2, 33, 31, 500)}[name]
+    heat = ref.decode_inputs(11, 2, n_cls, H, W, False, True)['heatmap'].reshape(2, -1)
+    if name == 'nan_first':                    # the complemented key 0, alone in its bucket in the first pass
+        heat[:, 17] = np.nan
+    elif name == 'alone_in_top_byte':          # every score below 0.5 but one: the selected key leaves after one pass
+        heat *= np.float32(0.49)
+        heat[0, 700], heat[1, 3] = 0.75, 0.75
+    elif name == 'last_byte_only':             # keys that differ in their last byte only: all four passes
+        rs = np.random.RandomState(12)
+        heat = np.stack([(0x3E000000 + rs.permutation(256)).astype(np.uint32).view(np.float32) for _ in range(2)])
+    elif name == 'constant':                   # 2046 equal keys: every kept row is a tie
+        heat[:] = 0.10065
+    return np.ascontiguousarray(heat, np.float32).reshape(2, n_cls, H, W), K
+
+
+@pytest.mark.parametrize("name", ['k_equals_n', 'nan_first', 'alone_in_top_byte', 'last_byte_only', 'constant'])
+def test_decode_select_edges_keep_the_stated_order(name):
+    """The kept flat indices equal the stated rule's (descending score, ties by ascending flat index, NaN first) where the
+    rank is the last one, the selected key is alone in its bucket early or never, and where all keys are equal."""
+    heat, K = _select_case(name)
+    _, n_cls, H, W = heat.shape
+    HW = H * W
+    d = ref.decode_inputs(5, 2, n_cls, H, W, False, True)
+    d['heatmap'] = heat
+    d['iou'] = np.broadcast_to(np.arange(HW, dtype=np.float32).reshape(1, 1, H, W), (2, 1, H, W)).copy()
+    lim = [-1e9, -1e9, -1e9, 1e9, 1e9, 1e9]
+    got = run_decode(d, K, None, lim)
+    want = ref.decode_bbox_from_heatmap(d['heatmap'], d['rot_cos'], d['rot_sin'], d['center'], d['center_z'], d['dim'],
+                                        ref.CFG_A['point_cloud_range'], ref.CFG_A['voxel_size'], ref.CFG_A['stride'],
+                                        iou=d['iou'], K=K, post_center_limit_range=lim)
+    for r, w in zip(got, want):
+        flat = r['pred_labels'].astype(np.int64) * HW + r['pred_iou'].astype(np.int64)
+        assert len(w['order']) == K and np.array_equal(flat, w['order'])
+        assert r['pred_scores'].tobytes() == w['pred_scores'].tobytes()
+
+
 def test_round_trip_targets_to_predicted_boxes():
     """Independent of the reference: targets from random boxes -> prediction maps written from those targets (a large
     logit at each `inds` cell, the regression maps filled from `target_boxes`) -> generate_predicted_boxes with the config's

@@ -591,6 +591,50 @@ def test_fov_plane_label_match_oracle(st):
             v += 1
 
 
+PLANE_SIZES = [3, 4, 5, 63, 64, 65, 511, 512, 513, 1025, 3073]
+
+
+def _tied_height_points(n):
+    """n candidates of a tilted ground whose heights are multiples of 1/64: many exactly equal values around both medians."""
+    rng = np.random.default_rng(n)
+    xy = rng.uniform(-40.0, 40.0, (n, 2)).astype(np.float32)
+    j = rng.integers(-4, 5, n)
+    z = np.round((-1.7 + 0.01 * xy[:, 0].astype(np.float64) + j / 64.0) * 64.0) / 64.0
+    return np.concatenate([xy, z[:, None].astype(np.float32), np.zeros((n, 1), np.float32)], axis=1)
+
+
+@pytest.fixture(scope="module")
+def tied_planes(st):
+    """One launch: a frame with one view for every size, every point of the frame a candidate; plane key = size."""
+    from dfu3d_amd.params import Params
+    p = Params()
+    pts = [_tied_height_points(n) for n in PLANE_SIZES]
+    V, cap_n = len(PLANE_SIZES), max(PLANE_SIZES)
+    fov_idx = np.zeros((V, cap_n), np.int32)
+    for v, n in enumerate(PLANE_SIZES):
+        fov_idx[v, :n] = np.arange(n)
+    plane = torch.zeros(V * 4, dtype=torch.float64, device=DEV)
+    st.plane_ransac(_t(np.concatenate(pts)), _t(np.cumsum([0] + PLANE_SIZES), torch.int32), _t(np.arange(V), torch.int32),
+                    _t(fov_idx.reshape(-1)), _t(PLANE_SIZES, torch.int32), V, cap_n, p.plane_max_hs, p.plane_range,
+                    p.ransac_trials, p.ransac_seed, _t(PLANE_SIZES, torch.int64),
+                    torch.zeros(V * cap_n, dtype=torch.int32, device=DEV), plane)
+    torch.cuda.synchronize()
+    return pts, plane.cpu().numpy().reshape(V, 4)
+
+
+@pytest.mark.parametrize("n", PLANE_SIZES)
+def test_plane_medians_with_tied_heights_match_oracle(tied_planes, n):
+    """Odd and even medians around a wave, around the workgroup and beyond the candidates kept in LDS, over heights with
+    many exact ties: the plane (its inlier threshold is the MAD of the heights) is the oracle's."""
+    pts, planes = tied_planes
+    v = PLANE_SIZES.index(n)
+    z = pts[v][:, 2].astype(np.float64)
+    assert np.median(np.abs(z - np.median(z))) > 0.0
+    want = O.plane_ransac(pts[v][:, :3], O.Params(), key=n)
+    assert np.isfinite(want).all() and want[3] < 1e29
+    np.testing.assert_allclose(planes[v], want, rtol=1e-9, atol=1e-9)
+
+
 # ------------------------------------------------------------------ a7/a8/a9
 def _bp_run(st, depth, cal, masks, max_points=100, max_voxels=1000000, key_axis=1, cap_vox=1 << 16):
     V, H, W = depth.shape
@@ -685,8 +729,11 @@ def test_backproject_without_the_middle_tier_takes_the_full_fp64_paths(st, monke
 
 @pytest.mark.parametrize("max_points,max_voxels,key_axis", [(100, 1000000, 1), (100, 1000000, 2),
                                                             (3, 1000000, 1), (1, 1000000, 2),
-                                                            (100, 500, 1), (2, 300, 1)])
+                                                            (100, 500, 1), (2, 300, 1),
+                                                            (256, 1000000, 1), (314, 1000000, 2)])
 def test_backproject_bin_matches_oracle(st, max_points, max_voxels, key_axis):
+    # (the fullest bins of view 1 hold 280, 280, 300, 300, 314 and 315 pixels, counted with the oracle's voxelizer: a cap of
+    # 256 puts the repair's rank at the end of a sweep of its 256 threads in six lists, 314 leaves one list of cap + 1)
     from dfu3d_amd import synth
     s = synth.make_scene(31, H=180, W=320, M=4, cams=3, dense=True, k_min=10, k_max=14)
     depth = s.depth.numpy().copy()
