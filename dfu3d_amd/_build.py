@@ -81,7 +81,7 @@ def build(force=False, verbose=False):
 # product's results.  They are loaded only through _lib.load_variant() -- by tests/ and tools/, never by the package.
 VARIANTS = {
     # packed min-(key|pixel) word with only 14 key bits: keys collide below the cut all the time, so the exact
-    # repair of k_bp_vox / k_ovf_* / k_bp_fix (practically never taken in the product build) does the work
+    # repair that k_bp_vox queues for k_bp_repair (practically never taken in the product build) does the work
     "keybits14": ["-DDFU3D_DBG_COMBO_KEYBITS=14"],
     # no middle tier: what float32 leaves undecided goes to k_bp_bin_amb -- the path the product build takes for a handful
     # of pixels per launch

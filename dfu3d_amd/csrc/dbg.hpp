@@ -2,7 +2,7 @@
 // lists the test / timing builds that do (VARIANTS).  Nothing here changes results except where it says so.
 //
 //   DFU3D_DBG_COMBO_KEYBITS=<n>  test build: the packed min-(key | pixel) word of the voxel table keeps only n key bits, so keys
-//                                collide all the time and the exact repair of k_bp_vox / k_ovf_* / k_bp_fix (practically never
+//                                collide all the time and the exact repair that k_bp_vox queues for k_bp_repair (practically never
 //                                taken in the product) does the work.  Same results as the product.
 //   DFU3D_DBG_NO_MID             test build: no middle tier of the bin classification -- everything float32 leaves undecided takes
 //                                the full fp64 kernel (k_bp_bin_amb).  Same results as the product.

@@ -940,7 +940,7 @@ __global__ __launch_bounds__(SCB) void k_bp_scan(int BW, int NJ, int tiles_x, co
     running += tot;
   }
   if (threadIdx.x == 0) {
-    n_vox[v] = running;                                   // voxels = first pixels (clamped by k_bp_finalize)
+    n_vox[v] = running;                                   // voxels = first pixels (clamped by k_bp_repair)
     if (running > cap_vox) atomicOr(status, DFU3D_ST_VOX_OVERFLOW);
   }
 }
@@ -1056,7 +1056,7 @@ __global__ __launch_bounds__(VXB) void k_bp_vox(
       key += 0.0;                                   // -0.0 -> +0.0 (round to nearest), every other value unchanged
       // over the cap ("the first max_points pixels" must be found), or two keys that agree in their top bits only
       if (cw > (uint32_t)max_points || ordered_key(key) != e_kmin) {
-        const int slot = atomicAdd(&n_q[v], 1);        // exact repair (k_ovf_*, k_bp_fix); the entry stays as it is
+        const int slot = atomicAdd(&n_q[v], 1);        // exact repair (k_bp_repair); the entry stays as it is
         if (slot < cap_q) { q_bins[(size_t)v * cap_q + slot] = (uint32_t)b; q_rank[(size_t)v * cap_q + slot] = k; }
         else atomicOr(status, DFU3D_ST_VOX_PTS_OVERFLOW);
         keep = true;
@@ -1080,107 +1080,95 @@ __global__ __launch_bounds__(VXB) void k_bp_vox(
   }
 }
 
-// ---- O1: bin id per pixel, exact classification, only for views with a repair queue ----
-// (The phases of the repair are device functions of (v, bx, gx) -- the view, this workgroup's index among the gx
-// workgroups that share the view's work with the grid's stride: the stage-by-stage entry point runs each as a kernel of
-// its own, a few workgroups per view; the chain runs all of them in ONE kernel, k_bp_repair, a workgroup per view.)
-__device__ __forceinline__ void ph_rebin(int v, int bx, int gx,
-    const float *__restrict__ depth, const ViewCalib *__restrict__ calib, const dfu3d_bin_geom &g, int W, int HW,
-    int key_axis, const int *__restrict__ n_q, uint32_t *__restrict__ pix_bin) {
-  if (n_q[v] == 0) return;                           // the usual case
-  const ViewCalib c = calib[v];
+// ---- the exact repair: O1..O5 and the clamp of n_vox in ONE launch, one workgroup of PB threads per view --------
+// A repair queue belongs to one view, so the order the phases need -- lists allocated before they are gathered, gathered
+// before the selection reads them -- is an order inside the view's workgroup: a barrier (and a fence: the phases hand
+// over through global memory) between two phases.  A view with an empty queue -- every view of all but pathological
+// passes -- clamps its n_vox and leaves.  No result depends on how a phase deals its work to the threads: list offsets
+// and the order inside a list come from atomics, and the selection does not depend on either.
+struct RepairArgs {
+  const float *depth;
+  const ViewCalib *calib;
+  const void *masks;
+  const int *n_inst;
+  void *table;
+  uint32_t *pix_bin, *q_list, *q_bins, *status;
+  int *q_cnt, *q_cursor, *q_rank, *n_q, *n_vox;
+  int64_t E_view, E_total;
+  int mask_format, max_inst, W, HW, key_axis, max_points, max_voxels, cap_vox, cap_q;
+  int lean;                              // the chain: a voxel under no instance mask stores its it_bits alone (LEAN of k_bp_vox)
+  VoxOut out;
+};
+
+// ---- O1: bin id per pixel, exact classification ----
+__device__ __forceinline__ void ph_rebin(const RepairArgs &a, const dfu3d_bin_geom &g, int v) {
+  const ViewCalib c = a.calib[v];
   const Recip rc = make_recip(c);
   bool rerr = false;
-  for (int pix = bx * PB + threadIdx.x; pix < HW; pix += gx * PB) {
+  for (int pix = threadIdx.x; pix < a.HW; pix += PB) {
     double key;
-    pix_bin[(size_t)v * HW + pix] = pixel_bin(c, rc, g, W, pix, depth[(size_t)v * HW + pix], key_axis, key, rerr);
+    a.pix_bin[(size_t)v * a.HW + pix] =
+        pixel_bin(c, rc, g, a.W, pix, a.depth[(size_t)v * a.HW + pix], a.key_axis, key, rerr);
   }
-}
-__global__ __launch_bounds__(PB) void k_bp_rebin(
-    const float *__restrict__ depth, const ViewCalib *__restrict__ calib, dfu3d_bin_geom g, int W, int HW,
-    int key_axis, const int *__restrict__ n_q, uint32_t *__restrict__ pix_bin) {
-  ph_rebin(blockIdx.y, blockIdx.x, gridDim.x, depth, calib, g, W, HW, key_axis, n_q, pix_bin);
 }
 
 // ---- O2: allocate a pixel list per queued bin ----------------------------------
 // rep[e] <- list base, cnt[e] <- OVF_FLAG | 0 (fill cursor), q_cnt <- count
-__device__ __forceinline__ void ph_ovf_alloc(int v, int bx, int gx, void *table, int64_t E_total, int64_t E_view, int cap_q,
-                            const uint32_t *__restrict__ q_bins,
-                            const int *__restrict__ n_q, int *__restrict__ q_cnt,
-                            int *__restrict__ q_cursor, int HW,
-                            uint32_t *__restrict__ status) {
-  const int no = min(n_q[v], cap_q);
-  const Table T = table_view(table, E_total);
-  for (int s = bx * blockDim.x + threadIdx.x; s < no; s += gx * blockDim.x) {
-    const int64_t e = (int64_t)v * E_view + q_bins[(size_t)v * cap_q + s];
+__device__ __forceinline__ void ph_ovf_alloc(const RepairArgs &a, int v) {
+  const int no = min(a.n_q[v], a.cap_q);
+  const Table T = table_view(a.table, a.E_total);
+  for (int s = threadIdx.x; s < no; s += PB) {
+    const int64_t e = (int64_t)v * a.E_view + a.q_bins[(size_t)v * a.cap_q + s];
     const int c = (int)T.cnt[e];
-    const int off = atomicAdd(&q_cursor[v], c);
-    if (off + c > HW) atomicOr(status, DFU3D_ST_VOX_PTS_OVERFLOW);   // cannot happen
-    q_cnt[(size_t)v * cap_q + s] = c;
+    const int off = atomicAdd(&a.q_cursor[v], c);
+    if (off + c > a.HW) atomicOr(a.status, DFU3D_ST_VOX_PTS_OVERFLOW);   // cannot happen
+    a.q_cnt[(size_t)v * a.cap_q + s] = c;
     T.rep[e] = (uint32_t)off;
     T.cnt[e] = OVF_FLAG;
   }
 }
-__global__ void k_ovf_alloc(void *table, int64_t E_total, int64_t E_view, int cap_q, const uint32_t *__restrict__ q_bins,
-                            const int *__restrict__ n_q, int *__restrict__ q_cnt, int *__restrict__ q_cursor, int HW,
-                            uint32_t *__restrict__ status) {
-  ph_ovf_alloc(blockIdx.y, blockIdx.x, gridDim.x, table, E_total, E_view, cap_q, q_bins, n_q, q_cnt, q_cursor, HW, status);
-}
 
 // ---- O3: gather the pixel indices of queued bins -------------------------------
-__device__ __forceinline__ void ph_ovf_gather(int v, int bx, int gx,
-    const uint32_t *__restrict__ pix_bin, void *table, int64_t E_total, int64_t E_view,
-    int HW, const int *__restrict__ n_q, uint32_t *__restrict__ q_list) {
-  if (n_q[v] == 0) return;                         // the usual case: a few workgroups per view leave at once
-  const Table T = table_view(table, E_total);
-  for (int base = bx * PBLK + threadIdx.x * PPT; base < HW; base += gx * PBLK) {
+__device__ __forceinline__ void ph_ovf_gather(const RepairArgs &a, int v) {
+  const Table T = table_view(a.table, a.E_total);
+  for (int base = threadIdx.x * PPT; base < a.HW; base += PBLK) {
     for (int k = 0; k < PPT; k++) {
       const int pix = base + k;
-      if (pix >= HW) break;
-      const uint32_t b = pix_bin[(size_t)v * HW + pix];
+      if (pix >= a.HW) break;
+      const uint32_t b = a.pix_bin[(size_t)v * a.HW + pix];
       if (b == NOBIN) continue;
-      const int64_t e = (int64_t)v * E_view + b;
+      const int64_t e = (int64_t)v * a.E_view + b;
       if (T.cnt[e] & OVF_FLAG) {
         const uint32_t pos = atomicAdd(&T.cnt[e], 1u) & ~OVF_FLAG;
-        q_list[(size_t)v * HW + T.rep[e] + pos] = (uint32_t)pix;
+        a.q_list[(size_t)v * a.HW + T.rep[e] + pos] = (uint32_t)pix;
       }
     }
   }
 }
-__global__ __launch_bounds__(PB) void k_ovf_gather(
-    const uint32_t *__restrict__ pix_bin, void *table, int64_t E_total, int64_t E_view,
-    int HW, const int *__restrict__ n_q, uint32_t *__restrict__ q_list) {
-  ph_ovf_gather(blockIdx.y, blockIdx.x, gridDim.x, pix_bin, table, E_total, E_view, HW, n_q, q_list);
-}
 
-// ---- O4: per overflow bin, T = max_points-th smallest pixel, kmin over pix<=T -
-__device__ __forceinline__ void ph_ovf_select(int v, int bx, int gx,
-    const float *__restrict__ depth, const ViewCalib *__restrict__ calib, int W, int HW,
-    int key_axis, int max_points, void *table, int64_t E_total, int64_t E_view,
-    int cap_ovf, const uint32_t *__restrict__ ovf_bins, const int *__restrict__ n_ovf,
-    const int *__restrict__ ovf_cnt, const uint32_t *__restrict__ ovf_list) {
+// ---- O4: per queued bin, T = max_points-th smallest pixel, kmin over pix<=T ---
+__device__ __forceinline__ void ph_ovf_select(const RepairArgs &a, int v) {
   __shared__ int hist[256];
   __shared__ unsigned long long s_sel[3];
   __shared__ unsigned long long s_min[4];
-  const int no = min(n_ovf[v], cap_ovf);
-  const Table T = table_view(table, E_total);
-  const ViewCalib c = calib[v];
+  const int no = min(a.n_q[v], a.cap_q);
+  const Table T = table_view(a.table, a.E_total);
+  const ViewCalib c = a.calib[v];
   const Recip rc = make_recip(c);
-  for (int s = bx; s < no; s += gx) {     // uniform per block
-  const int64_t e = (int64_t)v * E_view + ovf_bins[(size_t)v * cap_ovf + s];
-  const int n = ovf_cnt[(size_t)v * cap_ovf + s];
-  const uint32_t *lst = ovf_list + (size_t)v * HW + T.rep[e];
+  for (int s = 0; s < no; s++) {          // the whole workgroup per bin
+  const int64_t e = (int64_t)v * a.E_view + a.q_bins[(size_t)v * a.cap_q + s];
+  const int n = a.q_cnt[(size_t)v * a.cap_q + s];
+  const uint32_t *lst = a.q_list + (size_t)v * a.HW + T.rep[e];
   __syncthreads();
   // the max_points-th smallest pixel of the list, or its largest: a bin queued for two colliding keys is no longer than the
   // cap and keeps every pixel (block_select wants rank < n)
   const uint32_t thr =
-      block_select<256, 24, uint32_t>(n, min(n, max_points) - 1, [&](int i) { return lst[i]; }, hist, s_sel).key;
+      block_select<256, 24, uint32_t>(n, min(n, a.max_points) - 1, [&](int i) { return lst[i]; }, hist, s_sel).key;
   unsigned long long m = ~0ull;
   for (int i = threadIdx.x; i < n; i += 256) {
     const uint32_t pix = lst[i];
     if (pix <= thr) {
-      const unsigned long long k = ordered_key(
-          pixel_key(c, rc, W, (int)pix, depth[(size_t)v * HW + pix], key_axis));
+      const unsigned long long k = ordered_key(pixel_key(c, rc, a.W, (int)pix, a.depth[(size_t)v * a.HW + pix], a.key_axis));
       m = k < m ? k : m;
     }
   }
@@ -1197,8 +1185,7 @@ __device__ __forceinline__ void ph_ovf_select(int v, int bx, int gx,
   for (int i = threadIdx.x; i < n; i += 256) {
     const uint32_t pix = lst[i];
     if (pix <= thr && pix < rp) {
-      const unsigned long long k = ordered_key(
-          pixel_key(c, rc, W, (int)pix, depth[(size_t)v * HW + pix], key_axis));
+      const unsigned long long k = ordered_key(pixel_key(c, rc, a.W, (int)pix, a.depth[(size_t)v * a.HW + pix], a.key_axis));
       if (k == m) rp = pix;
     }
   }
@@ -1215,33 +1202,21 @@ __device__ __forceinline__ void ph_ovf_select(int v, int bx, int gx,
   }
   }
 }
-__global__ __launch_bounds__(256) void k_ovf_select(
-    const float *__restrict__ depth, const ViewCalib *__restrict__ calib, int W, int HW,
-    int key_axis, int max_points, void *table, int64_t E_total, int64_t E_view,
-    int cap_ovf, const uint32_t *__restrict__ ovf_bins, const int *__restrict__ n_ovf,
-    const int *__restrict__ ovf_cnt, const uint32_t *__restrict__ ovf_list) {
-  ph_ovf_select(blockIdx.y, blockIdx.x, gridDim.x, depth, calib, W, HW, key_axis, max_points, table, E_total, E_view,
-                cap_ovf, ovf_bins, n_ovf, ovf_cnt, ovf_list);
-}
 
-// ---- O5: outputs of the repaired bins ---------------------------------------------
-__device__ __forceinline__ void ph_fix(int v, int bx, int gx, bool lean,
-    const float *__restrict__ depth, const ViewCalib *__restrict__ calib,
-    const void *__restrict__ masks, int mask_format, const int *__restrict__ n_inst, int max_inst, int W,
-    int HW, int max_voxels, int64_t E_view, void *table, int64_t E_total, int cap_vox, const VoxOut &out, int cap_q,
-    const uint32_t *__restrict__ q_bins, const int *__restrict__ q_rank, const int *__restrict__ n_q) {
-  const int no = min(n_q[v], cap_q);
-  if (bx * 256 >= no) return;
-  const Table T = table_view(table, E_total);
-  const ViewCalib c = calib[v];
+// ---- O5: outputs of the repaired bins, entries back to clean -------------------------
+__device__ __forceinline__ void ph_fix(const RepairArgs &a, int v) {
+  const int no = min(a.n_q[v], a.cap_q);
+  if ((int)(threadIdx.x & ~63u) >= no) return;      // a wave without a bin (the last phase: no barrier behind it)
+  const Table T = table_view(a.table, a.E_total);
+  const ViewCalib c = a.calib[v];
   const Recip rc = make_recip(c);
-  const int m = masks ? min(max(n_inst[v], 0), max_inst) : 0;
-  for (int s = bx * 256 + threadIdx.x; s < no; s += gx * 256) {
-    const int64_t e = (int64_t)v * E_view + q_bins[(size_t)v * cap_q + s];
-    const int k = q_rank[(size_t)v * cap_q + s];
-    if (k < max_voxels)
-      emit_voxel(out, (size_t)v * cap_vox + k, c, rc, depth + (size_t)v * HW, W, T.rep[e], masks, mask_format, m,
-                 max_inst, HW, v, lean);
+  const int m = a.masks ? min(max(a.n_inst[v], 0), a.max_inst) : 0;
+  for (int s = threadIdx.x; s < no; s += PB) {
+    const int64_t e = (int64_t)v * a.E_view + a.q_bins[(size_t)v * a.cap_q + s];
+    const int k = a.q_rank[(size_t)v * a.cap_q + s];
+    if (k < a.max_voxels)
+      emit_voxel(a.out, (size_t)v * a.cap_vox + k, c, rc, a.depth + (size_t)v * a.HW, a.W, T.rep[e], a.masks,
+                 a.mask_format, m, a.max_inst, a.HW, v, a.lean != 0);
     T.kmin[e] = ~0ull;
     T.combo[e] = ~0ull;
     T.cnt[e] = 0u;
@@ -1249,59 +1224,23 @@ __device__ __forceinline__ void ph_fix(int v, int bx, int gx, bool lean,
     T.rep[e] = NOBIN;
   }
 }
-__global__ __launch_bounds__(256) void k_bp_fix(
-    const float *__restrict__ depth, const ViewCalib *__restrict__ calib,
-    const void *__restrict__ masks, int mask_format, const int *__restrict__ n_inst, int max_inst, int W,
-    int HW, int max_voxels, int64_t E_view, void *table, int64_t E_total, int cap_vox, VoxOut out, int cap_q,
-    const uint32_t *__restrict__ q_bins, const int *__restrict__ q_rank, const int *__restrict__ n_q) {
-  ph_fix(blockIdx.y, blockIdx.x, gridDim.x, false, depth, calib, masks, mask_format, n_inst, max_inst, W, HW, max_voxels,
-         E_view, table, E_total, cap_vox, out, cap_q, q_bins, q_rank, n_q);
-}
 
-__global__ void k_bp_finalize(int V, int max_voxels, int cap_vox, int *__restrict__ n_vox) {
-  const int v = blockIdx.x * blockDim.x + threadIdx.x;
-  if (v >= V) return;
-  n_vox[v] = min(min(n_vox[v], cap_vox), max_voxels);
-}
-
-// ---- the chain's repair: O1..O5 and the clamp of n_vox in ONE launch, one workgroup per view -------------------
-// A repair queue belongs to one view, so the order the phases need -- lists allocated before they are gathered, gathered
-// before the selection reads them -- is an order inside the view's workgroup: a barrier (and a fence: the phases hand
-// over through global memory) between two phases.  A view with an empty queue -- every view of all but pathological
-// passes -- clamps its n_vox and leaves: what six launches did there.  A view under repair does with one workgroup what
-// the stage-by-stage kernels share among 16 or 32; the results are the same (the phases are the same functions and
-// none depends on how the work is dealt: list offsets and the order inside a list come from atomics in both forms, and
-// the selection does not depend on either).
-struct RepairArgs {
-  const float *depth;
-  const ViewCalib *calib;
-  const void *masks;
-  const int *n_inst;
-  void *table;
-  uint32_t *pix_bin, *q_list, *q_bins, *status;
-  int *q_cnt, *q_cursor, *q_rank, *n_q, *n_vox;
-  int64_t E_view, E_total;
-  int mask_format, max_inst, W, HW, key_axis, max_points, max_voxels, cap_vox, cap_q, lean;
-  VoxOut out;
-};
-static_assert(PB == 256, "k_bp_repair: every phase with 256 threads");
-__global__ __launch_bounds__(256) void k_bp_repair(dfu3d_bin_geom g, RepairArgs a) {
+static_assert(PB == 256, "k_bp_repair: block_select<256> and the reductions of ph_ovf_select");
+__global__ __launch_bounds__(PB) void k_bp_repair(dfu3d_bin_geom g, RepairArgs a) {
   const int v = blockIdx.x;
-  if (threadIdx.x == 0) a.n_vox[v] = min(min(a.n_vox[v], a.cap_vox), a.max_voxels);     // (k_bp_finalize)
+  if (threadIdx.x == 0) a.n_vox[v] = min(min(a.n_vox[v], a.cap_vox), a.max_voxels);
   if (a.n_q[v] == 0) return;                          // the usual case (uniform per workgroup)
-  ph_rebin(v, 0, 1, a.depth, a.calib, g, a.W, a.HW, a.key_axis, a.n_q, a.pix_bin);
-  ph_ovf_alloc(v, 0, 1, a.table, a.E_total, a.E_view, a.cap_q, a.q_bins, a.n_q, a.q_cnt, a.q_cursor, a.HW, a.status);
+  ph_rebin(a, g, v);
+  ph_ovf_alloc(a, v);
   __threadfence();
   __syncthreads();
-  ph_ovf_gather(v, 0, 1, a.pix_bin, a.table, a.E_total, a.E_view, a.HW, a.n_q, a.q_list);
+  ph_ovf_gather(a, v);
   __threadfence();
   __syncthreads();
-  ph_ovf_select(v, 0, 1, a.depth, a.calib, a.W, a.HW, a.key_axis, a.max_points, a.table, a.E_total, a.E_view, a.cap_q,
-                a.q_bins, a.n_q, a.q_cnt, a.q_list);
+  ph_ovf_select(a, v);
   __threadfence();
   __syncthreads();
-  ph_fix(v, 0, 1, a.lean != 0, a.depth, a.calib, a.masks, a.mask_format, a.n_inst, a.max_inst, a.W, a.HW, a.max_voxels,
-         a.E_view, a.table, a.E_total, a.cap_vox, a.out, a.cap_q, a.q_bins, a.q_rank, a.n_q);
+  ph_fix(a, v);
 }
 
 // tier 1 (pixel_bin_fast) against the fp64 classification (pixel_bin) on n pseudo-random pixels of view 0:
@@ -1528,7 +1467,7 @@ extern "C" int64_t dfu3d_backproject_scratch_words(int32_t V, int32_t H, int32_t
 }
 
 // chain != 0: the launch sequence of dfu3d_pseudo_boxes (common.hpp: dfu3d_backproject_bin_chain) -- the same kernels
-// and phases, with the tables kept across calls, the lean voxel records and the repair in one launch
+// and phases, with the tables kept across calls and the lean voxel records
 static int backproject_bin_impl(
     const float *depth, const float *calib, const void *masks, int32_t mask_format, const int32_t *n_inst,
     int32_t V, int32_t max_inst, int32_t H, int32_t W, const dfu3d_bin_geom *geom,
@@ -1611,43 +1550,19 @@ static int backproject_bin_impl(
                          S.cap_q, S.q_bins, S.q_rank, S.n_q, status, V);
     DFU3D_LAUNCH_CHECK();
   }
-  if ((phases & DFU3D_BP_REPAIR) && chain) {
+  if (phases & DFU3D_BP_REPAIR) {
+    // exact repair of the queued bins (more than max_points pixels, or a key collision below the cut of the packed
+    // word), and the clamp of n_vox; the stage-by-stage caller gets the full record of every voxel (lean = 0)
     RepairArgs a;
     a.depth = depth; a.calib = cal; a.masks = masks; a.n_inst = n_inst; a.table = table;
     a.pix_bin = pix_bin; a.q_list = q_list; a.q_bins = S.q_bins; a.status = status;
     a.q_cnt = S.q_cnt; a.q_cursor = S.q_cursor; a.q_rank = S.q_rank; a.n_q = S.n_q; a.n_vox = n_vox;
     a.E_view = E_view; a.E_total = E_total;
     a.mask_format = mask_format; a.max_inst = max_inst; a.W = W; a.HW = HW; a.key_axis = key_axis;
-    a.max_points = geom->max_points_per_voxel; a.max_voxels = geom->max_voxels; a.cap_vox = cap_vox; a.cap_q = S.cap_q; a.lean = 1;
+    a.max_points = geom->max_points_per_voxel; a.max_voxels = geom->max_voxels; a.cap_vox = cap_vox; a.cap_q = S.cap_q;
+    a.lean = chain ? 1 : 0;
     a.out = out;
-    hipLaunchKernelGGL(k_bp_repair, dim3(V), dim3(256), 0, st, *geom, a);
-    DFU3D_LAUNCH_CHECK();
-  } else if (phases & DFU3D_BP_REPAIR) {
-    // exact repair of the queued bins (more than max_points pixels, or a key collision below the cut of the
-    // packed word); every kernel leaves at once for a view whose queue is empty
-    const int nblk = (HW + PB - 1) / PB;
-    // (grids of a few workgroups per view: the queues are empty in all but pathological passes, and 75 000 workgroups that
-    // start only to find that out cost 25 us per pass; a view under repair walks its pixels with the grid's stride)
-    hipLaunchKernelGGL(k_bp_rebin, dim3(nblk < 16 ? nblk : 16, V), dim3(PB), 0, st, depth, cal, *geom, W, HW,
-                       key_axis, S.n_q, pix_bin);
-    DFU3D_LAUNCH_CHECK();
-    const int ga = (S.cap_q + 255) / 256;
-    hipLaunchKernelGGL(k_ovf_alloc, dim3(ga < 16 ? ga : 16, V), dim3(256), 0, st, table, E_total, E_view, S.cap_q,
-                       S.q_bins, S.n_q, S.q_cnt, S.q_cursor, HW, status);
-    DFU3D_LAUNCH_CHECK();
-    const int nblk4 = (HW + PBLK - 1) / PBLK;
-    hipLaunchKernelGGL(k_ovf_gather, dim3(nblk4 < 16 ? nblk4 : 16, V), dim3(PB), 0, st, pix_bin, table, E_total,
-                       E_view, HW, S.n_q, q_list);
-    DFU3D_LAUNCH_CHECK();
-    hipLaunchKernelGGL(k_ovf_select, dim3(S.cap_q < 32 ? S.cap_q : 32, V), dim3(256), 0, st, depth, cal, W, HW,
-                       key_axis, geom->max_points_per_voxel, table, E_total, E_view, S.cap_q,
-                       S.q_bins, S.n_q, S.q_cnt, q_list);
-    DFU3D_LAUNCH_CHECK();
-    hipLaunchKernelGGL(k_bp_fix, dim3(ga < 16 ? ga : 16, V), dim3(256), 0, st, depth, cal, masks, mask_format, n_inst,
-                       max_inst, W, HW, geom->max_voxels, E_view, table, E_total, cap_vox, out, S.cap_q, S.q_bins, S.q_rank,
-                       S.n_q);
-    DFU3D_LAUNCH_CHECK();
-    hipLaunchKernelGGL(k_bp_finalize, dim3((V + 255) / 256), dim3(256), 0, st, V, geom->max_voxels, cap_vox, n_vox);
+    hipLaunchKernelGGL(k_bp_repair, dim3(V), dim3(PB), 0, st, *geom, a);
     DFU3D_LAUNCH_CHECK();
   }
   return DFU3D_OK;

@@ -200,7 +200,7 @@ int dfu3d_backproject_bin(const float *depth, const float *calib,
 #define DFU3D_BP_AMB 2     /* k_bp_bin_amb: the pixels float32 could not classify, in fp64           */
 #define DFU3D_BP_MARK 4    /* k_bp_scan: popcount prefix of the first-pixel bit map, list of occupied table segments */
 #define DFU3D_BP_VOX 8     /* k_bp_vox: walk over the occupied table segments: rank, representative, outputs, reset */
-#define DFU3D_BP_REPAIR 16 /* exact repair of bins over the cap / key collisions (no-ops when none)  */
+#define DFU3D_BP_REPAIR 16 /* k_bp_repair: exact repair of bins over the cap / key collisions (leaves at once when none), clamp of n_vox */
 #define DFU3D_BP_ALL 31
 
 /* ---- per-instance point sets (my_loader.py:547-565) ------------------------

@@ -1,6 +1,7 @@
 """The chain path (dfu3d_pseudo_boxes) without the work its result does not need: edge tables kept across calls,
-the repair in one launch, lean voxel records, fewer launches.  Every test compares against something the change
-did not touch: the stage-by-stage path (the kernels and launch sequence of the stage entry points are the parent's),
+lean voxel records, fewer launches.  Every test compares against something that does not share the code under test:
+the stage-by-stage path where its kernels and launch sequence differ from the chain's (the exact repair does not:
+both paths launch k_bp_repair, so there the independent references are the product build and the CPU oracle),
 a fresh workspace, or the CPU oracle."""
 import ctypes
 
@@ -125,10 +126,12 @@ def _run_144(chain):
 @pytest.mark.parametrize("variant", ["keybits14", "no_mid"])
 def test_fused_repair_equals_the_stage_by_stage_repair_at_144_views(variant, monkeypatch):
     """The test builds that force the exact repair (keybits14: a large share of the voxels is queued; no_mid: the full fp64
-    classification) at 24 bench frames in one launch: the chain -- k_bp_repair, one launch, one workgroup per view -- gives
-    the rows of the stage-by-stage path of the same build (k_bp_rebin .. k_bp_finalize as separate launches: the parent's
-    repair, unchanged) and of the product build, bit for bit; the voxels of dfu3d_backproject_bin of the test build equal
-    the product's; and the rows equal the oracle's on all 24 frames."""
+    classification) at 24 bench frames in one launch: the chain gives the rows of the stage-by-stage path of the same build
+    and of the product build, bit for bit; the voxels of dfu3d_backproject_bin of the test build equal the product's; and
+    the rows equal the oracle's on all 24 frames.  Both paths run the repair as k_bp_repair, one launch and one workgroup
+    per view (the chain with lean records, the stage path with the record of every voxel), so the two paths of one build
+    are no check of the repair against each other: the independent references are the product build's rows and voxels,
+    where practically nothing is queued, and the CPU oracle."""
     _need_gpu()
     from dfu3d_amd import _lib
     from dfu3d_amd.params import Params

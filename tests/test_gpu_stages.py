@@ -636,7 +636,9 @@ def test_plane_medians_with_tied_heights_match_oracle(tied_planes, n):
 
 
 # ------------------------------------------------------------------ a7/a8/a9
-def _bp_run(st, depth, cal, masks, max_points=100, max_voxels=1000000, key_axis=1, cap_vox=1 << 16):
+def _bp_run(st, depth, cal, masks, max_points=100, max_voxels=1000000, key_axis=1, cap_vox=1 << 16, calls=None):
+    """calls: the phase bits of each backproject_bin call of a pass (default: one call with every phase)."""
+    calls = calls or (st.BP_ALL,)
     V, H, W = depth.shape
     geom, E = st.make_geom(max_points_per_voxel=max_points, max_voxels=max_voxels)
     table = torch.empty(V * E * st.TABLE_ENTRY_BYTES, dtype=torch.uint8, device=DEV)
@@ -653,8 +655,9 @@ def _bp_run(st, depth, cal, masks, max_points=100, max_voxels=1000000, key_axis=
     pix_bin, blk = i32(pw), i32(bw)
     out = []
     for rep in range(2):            # second run proves the table was left clean
-        st.backproject_bin(_t(depth), calib, _t(masks), n_inst, V, M, H, W, geom, E, key_axis,
-                           table, pix_bin, blk, cap_vox, n_vox, vox_pix, bits, x, y, z, status)
+        for phases in calls:
+            st.backproject_bin(_t(depth), calib, _t(masks), n_inst, V, M, H, W, geom, E, key_axis,
+                               table, pix_bin, blk, cap_vox, n_vox, vox_pix, bits, x, y, z, status, phases=phases)
         torch.cuda.synchronize()
         out.append((n_vox.cpu().numpy().copy(), vox_pix.cpu().numpy().reshape(V, cap_vox).copy(),
                     bits.cpu().numpy().reshape(V, cap_vox).copy(),
@@ -679,10 +682,118 @@ def _bp_oracle(depth_v, cal, masks_v, max_points, max_voxels, key_axis):
     return pix, p0[rep], bits
 
 
+def _bp_assert_oracle(got, expected):
+    n_vox, vox_pix, bits, xyz, status = got
+    assert status == 0
+    for v, (pix, pts, ob) in enumerate(expected):
+        assert n_vox[v] == len(pix), (v, n_vox[v], len(pix))
+        assert np.array_equal(vox_pix[v, :len(pix)], pix), v
+        assert np.array_equal(bits[v, :len(pix)], ob), v
+        assert np.array_equal(xyz[v, :len(pix)], pts), v
+
+
+def _bp_oracle_bin_sizes(depth_v, cal):
+    """Pixels per occupied voxel of one view, from the oracle's voxel keys: the points voxel_sample keeps and the
+    cell orc_voxelize gives each of them (floor((coord - range_min) / size) per axis, inside the grid)."""
+    p = O.Params()
+    rows, cols, pl = O.backproject(depth_v.copy(), _oracle_calib(cal), p.depth_min)
+    pl = pl[pl[:, 2] < p.z_max]
+    if len(pl) == 0:
+        return np.zeros(0, np.int64)
+    r, theta, phi = O.to_sphere_coords(pl)
+    coords = np.stack([r, theta, phi], 1)[theta > p.theta_min]
+    grid = np.array(p.vgrid, np.int64)
+    with np.errstate(all="ignore"):
+        q = np.floor((coords - np.array(p.vrange_min, np.float64)) / np.array(p.vsize, np.float64))
+    q = q[np.all((q >= 0) & (q < grid), axis=1)].astype(np.int64)
+    cell = (q[:, 0] * grid[1] + q[:, 1]) * grid[2] + q[:, 2]
+    return np.unique(cell, return_counts=True)[1]
+
+
+@pytest.fixture(scope="module")
+def bp_mixed_views():
+    """Four views of 37 x 52 pixels (HW = 1924: no multiple of 256 or of 1024, W % 4 == 0), a window below the horizon
+    of a 180 x 320 scene with the principal points moved along: a generated view, an empty one between views under
+    repair, one of constant depth and one whose pixels all land in a handful of bins (lists many times the cap).
+    -> depth, calibrations, masks, pixels per bin of every view, and the oracle's answer per (max_points, key_axis),
+    computed once."""
+    from dfu3d_amd import synth
+    r0, c0, H, W = 96, 160, 37, 52
+    s = synth.make_scene(37, H=180, W=320, M=4, cams=4, dense=True, k_min=10, k_max=14)
+    depth = np.ascontiguousarray(s.depth.numpy()[:, r0:r0 + H, c0:c0 + W])
+    masks = np.ascontiguousarray(s.masks.numpy()[:, :, r0:r0 + H, c0:c0 + W])
+    cal = []
+    for c in s.calibs:
+        P2 = np.array(c.P2, np.float32)
+        P2[0, 2] -= c0
+        P2[1, 2] -= r0
+        cal.append(synth.Calibration({"P2": P2, "R0": c.R0, "Tr_velo2cam": c.V2C}))
+    depth[1] = 0.0
+    depth[2] = 7.5
+    depth[3] = 0.02
+    sizes = [_bp_oracle_bin_sizes(depth[v], cal[v]) for v in range(4)]
+    expected = {}
+
+    def oracle(max_points, key_axis):
+        if (max_points, key_axis) not in expected:
+            expected[max_points, key_axis] = [_bp_oracle(depth[v], cal[v], masks[v], max_points, 1000000, key_axis)
+                                              for v in range(4)]
+        return expected[max_points, key_axis]
+    return depth, cal, masks, sizes, oracle
+
+
+@pytest.mark.parametrize("variant", [None, "keybits14"])
+@pytest.mark.parametrize("max_points,key_axis", [(1, 1), (1, 2), (100, 1), (100, 2)])
+def test_backproject_repair_odd_sizes_and_mixed_views(st, monkeypatch, bp_mixed_views, max_points, key_axis, variant):
+    """The repair at a size that is no multiple of a sweep of its workgroup, with an empty queue between two views
+    under repair, in the product build and in the build whose keys collide all the time: the oracle's answer, bit
+    for bit (_bp_run's second pass proves the table clean)."""
+    from dfu3d_amd import _lib
+    depth, cal, masks, sizes, oracle = bp_mixed_views
+    assert sizes[0].max() > 1 and len(sizes[1]) == 0 and len(sizes[2]) > 0      # (a bin over the cap of 1, nothing, something)
+    assert len(sizes[3]) <= 16 and sizes[3].sum() == 37 * 52 and sizes[3].max() > 100
+    if variant:
+        monkeypatch.setattr(_lib, "_LIB", _lib.load_variant(variant))
+    _bp_assert_oracle(_bp_run(st, depth, cal, masks, max_points, 1000000, key_axis), oracle(max_points, key_axis))
+
+
+def test_backproject_repair_queue_and_lists_longer_than_one_sweep(st):
+    """A view with more than 256 queued bins and a bin with more than 256 pixels (both counted on the CPU from the
+    oracle's voxel keys): the 256 threads of the repair go over the queue (allocation, outputs) and over a list
+    (selection) more than once."""
+    from dfu3d_amd import synth
+    s = synth.make_scene(31, H=180, W=320, M=4, cams=3, dense=True, k_min=10, k_max=14)
+    depth = s.depth.numpy().copy()
+    depth[0, 100:110, :] = 7.5
+    depth[1, 60:90, 100:200] = 0.02
+    masks = s.masks.numpy()
+    sizes = [_bp_oracle_bin_sizes(depth[v], s.calibs[v]) for v in range(3)]
+    assert max(int((n > 1).sum()) for n in sizes) > 256         # bins over the cap of 1 in one view
+    assert max(int(n.max()) for n in sizes) > 256               # pixels of one bin
+    _bp_assert_oracle(_bp_run(st, depth, s.calibs, masks, 1, 1000000, 1),
+                      [_bp_oracle(depth[v], s.calibs[v], masks[v], 1, 1000000, 1) for v in range(3)])
+
+
+@pytest.mark.parametrize("variant,max_points", [(None, 2), ("keybits14", 100)])
+def test_backproject_repair_in_a_call_of_its_own(st, monkeypatch, bp_mixed_views, variant, max_points):
+    """DFU3D_BP_REPAIR issued alone after the other four phases (what the timing engine does) gives the result of
+    one call with every phase, bit for bit: voxels, records, status, and a clean table after the pass."""
+    from dfu3d_amd import _lib
+    depth, cal, masks, _, _ = bp_mixed_views
+    if variant:
+        monkeypatch.setattr(_lib, "_LIB", _lib.load_variant(variant))
+    one = _bp_run(st, depth, cal, masks, max_points, 1000000, 1)
+    two = _bp_run(st, depth, cal, masks, max_points, 1000000, 1,
+                  calls=(st.BP_BIN | st.BP_AMB | st.BP_MARK | st.BP_VOX, st.BP_REPAIR))
+    assert one[4] == two[4] == 0
+    for a, b in zip(one[:4], two[:4]):
+        assert np.array_equal(a, b)
+
+
 def test_backproject_repair_path_with_colliding_keys(st, monkeypatch):
     """Test build of the library whose packed min-(key|pixel) word keeps only 14 key bits: the cheap representative
-    is wrong for a large share of the voxels, so k_bp_vox queues them and the exact repair (k_bp_rebin, k_ovf_*,
-    k_bp_fix) produces the answer -- it must still be the oracle's, bit for bit."""
+    is wrong for a large share of the voxels, so k_bp_vox queues them and the exact repair (k_bp_repair, one
+    workgroup per view) produces the answer -- it must still be the oracle's, bit for bit."""
     from dfu3d_amd import _lib, synth
     L = _lib.load_variant("keybits14")
     monkeypatch.setattr(_lib, "_LIB", L)
