@@ -26,6 +26,21 @@ __device__ __forceinline__ BoxF load_box(const double *b) {
   return q;
 }
 
+// The same box from float32 (x, y, z, dx, dy, dz, heading) with the margin of the caller's op (roipoint_stage.hip: 1e-5f)
+// and its enlargement of the dims, added in float32 as box_utils.enlarge_box3d does.  The float64 centre is the float one.
+__device__ __forceinline__ BoxF load_box_f32(const float *b, float margin, float ex, float ey, float ez) {
+  BoxF q;
+  q.cx = b[0]; q.cy = b[1]; q.cz = b[2];
+  q.c64x = (double)q.cx; q.c64y = (double)q.cy; q.c64z = (double)q.cz;
+  const float dx = b[3] + ex, dy = b[4] + ey, dz = b[5] + ez, rz = b[6];
+  q.cosa = (float)cos((double)(-rz));
+  q.sina = (float)sin((double)(-rz));
+  q.hz = (double)dz / 2.0;
+  q.hx = (double)dx / 2.0 + (double)margin;
+  q.hy = (double)dy / 2.0 + (double)margin;
+  return q;
+}
+
 __device__ __forceinline__ bool pt_in_box(const BoxF &q, float x, float y, float z) {
   if ((double)fabsf(z - q.cz) > q.hz) return false;
   const float sx = x - q.cx, sy = y - q.cy;

@@ -61,3 +61,27 @@ def boxes3d_kitti_camera_to_lidar(boxes3d_camera, calib):
     xyz_lidar = calib.rect_to_lidar(b[:, 0:3])
     xyz_lidar[:, 2] += h[:, 0] / 2
     return np.concatenate([xyz_lidar, l, w, h, -(r + np.pi / 2)], axis=-1)
+
+
+def enlarge_box3d(boxes3d, extra_width=(0, 0, 0)):
+    """(N, 7 + C) [x y z dx dy dz heading ...], NumPy or torch -> a copy (torch) with extra_width added to dx, dy, dz in
+    the boxes' dtype (box_utils.py:187-200)."""
+    import torch
+    boxes3d = torch.from_numpy(boxes3d).float() if isinstance(boxes3d, np.ndarray) else boxes3d
+    large = boxes3d.clone()
+    large[:, 3:6] += boxes3d.new_tensor(extra_width)[None, :]
+    return large
+
+
+def rotate_points_along_z(points, angle):
+    """points (B, N, 3 + C), angle (B) about z, x towards y -> the rotated points, the other columns unchanged
+    (common_utils.py:35-57): [x', y'] = [x cos - y sin, x sin + y cos]."""
+    import torch
+    is_numpy = isinstance(points, np.ndarray)
+    points = torch.from_numpy(points).float() if is_numpy else points
+    angle = torch.from_numpy(angle).float() if isinstance(angle, np.ndarray) else angle
+    cosa, sina = torch.cos(angle), torch.sin(angle)
+    zeros, ones = angle.new_zeros(points.shape[0]), angle.new_ones(points.shape[0])
+    rot = torch.stack((cosa, sina, zeros, -sina, cosa, zeros, zeros, zeros, ones), dim=1).view(-1, 3, 3).float()
+    out = torch.cat((torch.matmul(points[:, :, 0:3], rot), points[:, :, 3:]), dim=-1)
+    return out.numpy() if is_numpy else out
