@@ -446,6 +446,10 @@ __global__ void k_bp_tables_forget(BinCold *cold, int *tab_done) {
   if (threadIdx.x == 0) *tab_done = 0;
 }
 
+// The reference's depth test (my_loader.py:507-509), one statement for tier 1 and for the empty-tile vote of k_bp_bin: false
+// for a NaN, for zero and negative depths and for depths below depth_min
+__device__ __forceinline__ bool depth_live(float d, float depth_min) { return (d >= depth_min) && (d > 0.0f); }
+
 __device__ __forceinline__ void backproject_f32(const FastCal &fc, int col, int row, float d, float &xf, float &yf,
                                                 float &zf, float &err) {
   const float u = (float)col, v = (float)row;
@@ -485,7 +489,7 @@ __device__ __forceinline__ void classify_fast(const FastCal &fc, const HotGeom &
 #pragma unroll
   for (int k = 0; k < N; k++) {
     backproject_f32(fc, col[k], row, d[k], xf[k], yf[k], zf[k], err[k]);
-    const bool dok = (d[k] >= fg.depth_min) && (d[k] > 0.0f);      // my_loader.py:507-509
+    const bool dok = depth_live(d[k], fg.depth_min);
     dead[k] = !dok || (zf[k] > fg.z_max + err[k]);                       // certainly z >= z_max (my_loader.py:540)
     any_live = any_live || !dead[k];
     res[k] = NOBIN; it[k] = 0; ip[k] = 0;
@@ -621,6 +625,13 @@ constexpr int P1_OCC = 7;                          // workgroups per compute uni
                                                    // still over eight's 64 / 80
 constexpr int RPT = 2;                             // rows per thread: a workgroup's tile is TILE_W x (RPT * TILE_H) pixels --
                                                    // the window set-up, its flush and the reductions are paid once per 2048 pixels
+// What a tile without a live pixel costs (44.6 % of the bench workload's workgroups: sky and holes of the depth map): the
+// set-up, two depth loads per thread, eight depth tests, a ballot and one barrier -- thread 0 spends 29 k cycles there, mostly
+// waiting for the loads, against 261 k in a workgroup that goes on (profiles/r08_p1_timing.log).  The vote itself is paid by every
+// workgroup: statically 2319 vector + 1084 scalar instructions before, 2349 + 974 now (profiles/r08_isa_mix.txt).  Until round 8 such a tile also paid the
+// window reset, the float32 back-projection of its pixels, the packing, both origin reductions and all four barriers: 400-450
+// vector instructions per wave for nothing.  Measured with tools/ab_builds.py (bp_bin per 384-view pass): 2.39 ms before, 2.34
+// with the packing of the results written as selects alone, 2.25 with the exit as well (profiles/r08_ab_bench.log).
 __global__ __launch_bounds__(PB, P1_OCC) void k_bp_bin(
     const float *__restrict__ depth, const ViewCalib *__restrict__ calib,
     const FastCal *__restrict__ fastcal, const float2 *__restrict__ tab, HotGeom hg, int W, int H, int tiles_x, int tiles_y, int key_axis,
@@ -633,6 +644,7 @@ __global__ __launch_bounds__(PB, P1_OCC) void k_bp_bin(
   __shared__ unsigned long long s_kmin[WIN_T * WIN_P], s_combo[WIN_T * WIN_P];
   __shared__ uint32_t s_cnt[WIN_T * WIN_P], s_first[WIN_T * WIN_P];
   __shared__ int s_namb, s_t0, s_p0;
+  __shared__ uint32_t s_live[PB / DFU3D_WAVE];    // per wave: one of its pixels passes the depth test
   DBG_T_START();
   DBG_T_COUNT(8);
   const int v = blockIdx.y;
@@ -678,45 +690,74 @@ __global__ __launch_bounds__(PB, P1_OCC) void k_bp_bin(
   auto global_pix = [&](uint32_t loc) { return pix00 + __umul24(loc >> 6, (uint32_t)W) + (loc & 63u); };
   static_assert(TILE_W == 64, "tile-local pixel index");
   static_assert(WIN_T * WIN_P % PB == 0, "window reset and flush: every thread takes the same number of slots");
-#pragma unroll
-  for (int j = 0; j < WIN_T * WIN_P / PB; j++) {
-    const int i = threadIdx.x + j * PB;
-    s_kmin[i] = ~0ull; s_combo[i] = ~0ull; s_cnt[i] = 0u; s_first[i] = NOBIN;
-  }
-  __syncthreads();
-  DBG_T(0);                                        // set-up: records, window reset, barrier
-  // what a kept pixel carries across the origin's barrier: its window coordinates in ONE word (theta | phi << 16; NOBIN: not
-  // kept) and its depth -- the exact fp64 key is formed where it is used, behind the barrier.  (Until round 4: the bin
-  // index, the two coordinates and the key, 40 registers instead of 16, and the kernel sat at 93 of them, five waves
-  // per SIMD.)
-  uint32_t tp[RPT][PPT];
+  // THE EXIT of the tile without a live pixel (sky, holes of the depth map: 45 % of the bench workload's tiles).  The thread's
+  // RPT * PPT depths are loaded first and put to tier 1's own depth test; a pixel outside the image counts as dead (its
+  // depth stays 0).  Every wave writes its vote to a word of its own -- nothing to initialise -- and behind the set-up's
+  // barrier a workgroup with four zero votes returns: it has touched neither the window nor the table, the bit map,
+  // the occupancy bytes or a list.  The depths stay in registers for tier 1 (eight registers up to the origin's barrier).
+  float d[RPT][PPT];
   bool inside[RPT];
-  int tmin = 0x7FFFFFFF, pmin = 0x7FFFFFFF;
-  uint32_t amb_mask = 0u;                         // bit r * PPT + k: pixel k of the thread's row r is undecided
 #pragma unroll
   for (int r = 0; r < RPT; r++) {
     const int row = row0 + r * TILE_H;
     inside[r] = (row < H) && (col < W);
 #pragma unroll
+    for (int k = 0; k < PPT; k++) d[r][k] = 0.0f;
+    if (inside[r]) load4(depth_v, __umul24((uint32_t)row, (uint32_t)W) + (uint32_t)col, d[r]);
+  }
+  bool live = false;
+#pragma unroll
+  for (int r = 0; r < RPT; r++)
+#pragma unroll
+    for (int k = 0; k < PPT; k++) live = live || depth_live(d[r][k], hg.depth_min);
+  const bool wave_live = __ballot(live) != 0ull;
+  if (lane_id() == 0) s_live[threadIdx.x >> 6] = wave_live ? 1u : 0u;
+  __syncthreads();
+  DBG_T(0);                                        // set-up: records, depth loads, vote, barrier
+  static_assert(PB / DFU3D_WAVE == 4, "one vote per wave");
+  if ((s_live[0] | s_live[1] | s_live[2] | s_live[3]) == 0u) {
+    DBG_T_COUNT(9);
+    DBG_T_ADD(10, clock64() - dbg_t0_);
+    return;
+  }
+  // The window reset, behind the vote: an empty workgroup does not pay it, and the origin's barrier still lies between it
+  // and the first window atomic.  (Issued between the depth loads and their use instead, under the loads' latency, every
+  // workgroup pays its 24 LDS stores per thread: 2.31 ms against 2.27 in one run of tools/ab_builds.py.)
+#pragma unroll
+  for (int j = 0; j < WIN_T * WIN_P / PB; j++) {
+    const int i = threadIdx.x + j * PB;
+    s_kmin[i] = ~0ull; s_combo[i] = ~0ull; s_cnt[i] = 0u; s_first[i] = NOBIN;
+  }
+  // what a kept pixel carries across the origin's barrier: its window coordinates in ONE word (theta | phi << 16; NOBIN: not
+  // kept) and its depth -- the exact fp64 key is formed where it is used, behind the barrier.  (Until round 4: the bin
+  // index, the two coordinates and the key, 40 registers instead of 16, and the kernel sat at 93 of them, five waves
+  // per SIMD.)
+  uint32_t tp[RPT][PPT];
+  int tmin = 0x7FFFFFFF, pmin = 0x7FFFFFFF;
+  uint32_t amb_mask = 0u;                         // bit r * PPT + k: pixel k of the thread's row r is undecided
+#pragma unroll
+  for (int r = 0; r < RPT; r++) {
+    const int row = row0 + r * TILE_H;
+#pragma unroll
     for (int k = 0; k < PPT; k++) tp[r][k] = NOBIN;
     if (!inside[r]) continue;
-    float d[PPT];
-    load4(depth_v, __umul24((uint32_t)row, (uint32_t)W) + (uint32_t)col, d);
     int cols[PPT];
 #pragma unroll
     for (int k = 0; k < PPT; k++) cols[k] = col + k;
     uint32_t res[PPT];
     int its[PPT], ips[PPT];
-    classify_fast<PPT>(fc, hg, tab, row, cols, d, res, its, ips);
+    classify_fast<PPT>(fc, hg, tab, row, cols, d[r], res, its, ips);
 #pragma unroll
     for (int k = 0; k < PPT; k++) {
       const uint32_t b = res[k];
-      if (b == AMBIG) {
-        amb_mask |= 1u << (r * PPT + k);
-      } else if (b != NOBIN) {
-        tp[r][k] = (uint32_t)its[k] | ((uint32_t)ips[k] << 16);
-        tmin = min(tmin, its[k]); pmin = min(pmin, ips[k]);
-      }
+      // selects, no branches (NOBIN and AMBIG are the two largest values).  As `if (b == AMBIG) .. else if (b != NOBIN) ..`
+      // every pixel compiled to a chain of exec-mask blocks.  Compared on the tuning build that still had a second exit (below):
+      // statically 2363 vector + 1105 scalar instructions in the kernel with the branches, 2354 + 983 with the selects
+      // (tools/isa_mix.py), 2.30 ms against 2.26 (tools/ab_builds.py)
+      const bool kept = b < AMBIG;
+      amb_mask |= (b == AMBIG ? 1u : 0u) << (r * PPT + k);
+      tp[r][k] = kept ? ((uint32_t)its[k] | ((uint32_t)ips[k] << 16)) : NOBIN;
+      tmin = min(tmin, kept ? its[k] : 0x7FFFFFFF); pmin = min(pmin, kept ? ips[k] : 0x7FFFFFFF);
     }
   }
   // the thread's undecided pixels (0.7 % of the pixels): one request for list slots per thread, not one per pixel
@@ -731,7 +772,7 @@ __global__ __launch_bounds__(PB, P1_OCC) void k_bp_bin(
       slot++;
     }
   }
-  DBG_T(1);                                        // depth loads, classification, exact keys (thread 0's wave)
+  DBG_T(1);                                        // window reset, classification, list of undecided pixels
   // window origin: wave minimum first (all lanes), then one LDS atomic per wave -- 256 lanes on two
   // addresses serialise
   tmin = wave_min_i_dpp(tmin);
@@ -739,6 +780,11 @@ __global__ __launch_bounds__(PB, P1_OCC) void k_bp_bin(
   if (lane_id() == 0 && tmin != 0x7FFFFFFF) { atomicMin(&s_t0, tmin); atomicMin(&s_p0, pmin); }
   __syncthreads();
   const int t0 = s_t0, p0 = s_p0;
+  // A tile whose live pixels tier 1 has all dropped (z >= z_max or theta <= theta_min for certain) has no kept pixel -- the
+  // origin was never lowered -- and no undecided one: everything below does nothing for it.  NO second exit here: 0.3 % of the
+  // bench workload's workgroups are of this kind (its sky has no depth at all), and returning at this point measured 2.256 ms
+  // against 2.249 without (tools/ab_builds.py): no gain.  The timing build counts them.
+  if (t0 == 0x7FFFFFFF && s_namb == 0) DBG_T_COUNT(11);
   const KeyCal kcal = key_cal(c);
   const Recip rc = recip_of(fc);
   const KeyCol kcol = load_key_col(calib + v, key_axis);
@@ -855,7 +901,8 @@ __global__ __launch_bounds__(PB, P1_OCC) void k_bp_bin(
   DBG_T(6);                                        // barrier
   // the workgroup's own bits: contiguous 128-byte wave atomics, one per bit-map tile (XOR: other tiles may already
   // have toggled here)
-  if (wave0 && s_bits[threadIdx.x]) {
+  // (the first wave again, from threadIdx.x: `wave0` kept from the entry to here costs three more spilled scalar registers)
+  if (threadIdx.x < DFU3D_WAVE && s_bits[threadIdx.x & 63]) {
     const int sub = threadIdx.x >> 5;                             // which of the RPT bit-map tiles
     if (ty * RPT + sub < tiles_y)
       atomicXor(&at32(bitmap_v, (uint32_t)(((ty * RPT + sub) * tiles_x + tx) * 32) + (threadIdx.x & 31)), s_bits[threadIdx.x]);
@@ -864,6 +911,7 @@ __global__ __launch_bounds__(PB, P1_OCC) void k_bp_bin(
   DBG_T(7);                                        // bit-map flush
   for (int i = threadIdx.x; i < na; i += PB)      // (what the middle tier left: in practice nothing)
     if (s_amb[i] != NOBIN) at32(amb_v, (uint32_t)atomicAdd(&n_amb[v], 1)) = s_amb[i];
+  DBG_T_ADD(12, clock64() - dbg_t0_);              // (a workgroup that did not take the exit, entry to end)
 }
 
 

@@ -25,10 +25,20 @@ L.dfu3d_debug_timing_pixel(out, 1)
 eng.run(batch); torch.cuda.synchronize()
 L.dfu3d_debug_timing_pixel(out, 1)
 v = list(out)
+# slots: 0-7 cycles of the phases, 8 workgroups, 9 / 10 workgroups that left at the exit (no live pixel) and their cycles from
+# entry to exit, 11 workgroups with live pixels of which none is kept or undecided (they have no exit of their own), 12 cycles
+# from entry to end of the workgroups that went on
 wg = max(v[8], 1)
-names = ["set-up + barrier", "loads, classification, exact keys", "origin reduction + barrier", "run merging + LDS atomics",
+n1, n2 = v[9], v[11]
+live = max(v[8] - n1, 1)
+names = ["set-up, depth loads, vote + barrier", "window reset, classification", "origin reduction + barrier", "run merging + LDS atomics",
          "barrier", "flush (global atomics issued)", "barrier", "bit-map flush"]
-tot = sum(v[:8])
-print("k_bp_bin: %d workgroups, %.0f cycles per workgroup (thread 0)" % (v[8], tot / wg))
+print("k_bp_bin: %d workgroups (thread 0's cycles)" % v[8])
+print("  exit (no live pixel):         %8d workgroups  %5.1f %%  %7.0f cycles each" % (n1, 100.0 * n1 / wg, v[10] / max(n1, 1)))
+print("  going on:                     %8d workgroups  %5.1f %%  %7.0f cycles each" % (v[8] - n1, 100.0 * (v[8] - n1) / wg, v[12] / live))
+print("    live, nothing kept:         %8d workgroups  %5.1f %%  (no exit of their own)" % (n2, 100.0 * n2 / wg))
+# the first phase is every workgroup's, the others only those of the workgroups that went on: each average over its own
+print("  phase                                  cycles per workgroup that ran it   share of all cycles")
+tot = max(sum(v[:8]), 1)
 for i, nm in enumerate(names):
-    print("  %-36s %9.0f cycles  %5.1f %%" % (nm, v[i] / wg, 100.0 * v[i] / max(tot, 1)))
+    print("  %-36s %9.0f  (%6d workgroups)  %5.1f %%" % (nm, v[i] / (wg if i == 0 else live), v[8] if i == 0 else v[8] - n1, 100.0 * v[i] / tot))
