@@ -35,7 +35,8 @@ def _deps():
                os.path.join(INCLUDE, "dfu3d_head.h"), os.path.join(INCLUDE, "dfu3d_post.h"),
                os.path.join(INCLUDE, "dfu3d_aug.h"), os.path.join(INCLUDE, "dfu3d_bev.h"),
                os.path.join(INCLUDE, "dfu3d_opt.h"), os.path.join(INCLUDE, "dfu3d_ingest.h"),
-               os.path.join(INCLUDE, "dfu3d_pn2.h"), os.path.join(INCLUDE, "dfu3d_roi.h")])
+               os.path.join(INCLUDE, "dfu3d_pn2.h"), os.path.join(INCLUDE, "dfu3d_roi.h"),
+               os.path.join(INCLUDE, "dfu3d_tgt.h")])
 
 
 def _stale(out):

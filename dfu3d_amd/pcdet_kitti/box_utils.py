@@ -85,3 +85,15 @@ def rotate_points_along_z(points, angle):
     rot = torch.stack((cosa, sina, zeros, -sina, cosa, zeros, zeros, zeros, ones), dim=1).view(-1, 3, 3).float()
     out = torch.cat((torch.matmul(points[:, :, 0:3], rot), points[:, :, 3:]), dim=-1)
     return out.numpy() if is_numpy else out
+
+
+CORNER_SIGNS = ((1, 1, -1), (1, -1, -1), (-1, -1, -1), (-1, 1, -1), (1, 1, 1), (1, -1, 1), (-1, -1, 1), (-1, 1, 1))
+
+
+def boxes_to_corners_3d(boxes3d):
+    """(N, 7) [x y z dx dy dz heading] torch -> (N, 8, 3): corners 0-3 the bottom face, 4-7 the top face, each face
+    counter-clockwise from (+x, +y) in the box frame as CORNER_SIGNS lists them (box_utils.py:28-53)."""
+    half = boxes3d.new_tensor(CORNER_SIGNS) / 2
+    corners = boxes3d[:, None, 3:6].repeat(1, 8, 1) * half[None, :, :]
+    corners = rotate_points_along_z(corners.view(-1, 8, 3), boxes3d[:, 6]).view(-1, 8, 3)
+    return corners + boxes3d[:, None, 0:3]

@@ -5,14 +5,20 @@ names and its `global_step` buffer, so a reference checkpoint's 'model_state' lo
 The inference path: `forward(batch_dict)` in eval mode returns (pred_dicts, recall_dict).  `post_processing` handles the
 whole batch in one chain -- sigmoid, a descending sort of every sample's scores, the count at or above SCORE_THRESH (a
 prefix after the sort), ONE segmented rotated NMS (iou3d_nms_utils.nms_gpu_segments), one gather -- and reads the B
-survivor counts from the device once.  Training (`get_training_loss`) is the row after this one and raises
-NotImplementedError."""
+survivor counts from the device once.
+
+Training is opt-in: `PointRCNN(..., trainable=True)` passes the keyword to both heads, which then build their loss
+functions and the proposal target layer (no parameters, no buffers: the state dict and its order do not change, and a
+checkpoint moves between a trainable and a default model with strict=True).  In training mode `forward` then returns
+({'loss': loss}, tb_dict, disp_dict) as train_utils' model_func expects, `get_training_loss` being the point head's loss
+plus the RoI head's with ONE copy to the host for the whole tb_dict (none with as_tensors=True).  Without the keyword
+training raises NotImplementedError as before."""
 import torch
 import torch.nn as nn
 
 from . import iou3d_nms_utils
 from .centerpoint import CenterPoint, _Dataset, _get
-from .point_head_box import TRAINING_ROW, PointHeadBox
+from .point_head_box import TRAINING_ROW, PointHeadBox, host_values
 from .pointnet2_backbone import PointNet2MSG
 from .pointrcnn_head import PointRCNNHead
 
@@ -33,10 +39,11 @@ def _module_class(model_cfg, section):
 
 
 class PointRCNN(nn.Module):
-    def __init__(self, model_cfg, num_class, dataset=None, **kwargs):
+    def __init__(self, model_cfg, num_class, dataset=None, trainable=False, **kwargs):
         """dataset: an object with class_names and point_feature_encoder.num_point_features -- or the same as keywords
-        (num_point_features for the last)."""
+        (num_point_features for the last).  trainable: build the training half of both heads."""
         super().__init__()
+        self.trainable = bool(trainable)
         if dataset is None:
             feats = kwargs.pop('num_point_features')
             dataset = _Dataset(point_feature_encoder=_Dataset(num_point_features=feats), **kwargs)
@@ -56,10 +63,11 @@ class PointRCNN(nn.Module):
             raise NotImplementedError("PointRCNN: POINT_HEAD.USE_POINT_FEATURES_BEFORE_FUSION (the backbone has none)")
         self.point_head = cls(model_cfg=cfg, input_channels=num_point_features,
                               num_class=num_class if not _get(cfg, 'CLASS_AGNOSTIC', False) else 1,
-                              predict_boxes_when_training=bool(_get(model_cfg, 'ROI_HEAD', False)))
+                              predict_boxes_when_training=bool(_get(model_cfg, 'ROI_HEAD', False)),
+                              trainable=self.trainable)
         cfg, cls = _module_class(model_cfg, 'ROI_HEAD')
         self.roi_head = cls(model_cfg=cfg, input_channels=num_point_features,
-                            num_class=num_class if not _get(cfg, 'CLASS_AGNOSTIC', False) else 1)
+                            num_class=num_class if not _get(cfg, 'CLASS_AGNOSTIC', False) else 1, trainable=self.trainable)
         self.module_list = [self.backbone_3d, self.point_head, self.roi_head]
 
     @property
@@ -70,14 +78,24 @@ class PointRCNN(nn.Module):
         self.global_step += 1
 
     def forward(self, batch_dict):
-        if self.training:
+        if self.training and not self.trainable:
             raise NotImplementedError("PointRCNN.forward in training mode: " + TRAINING_ROW)
         for cur_module in self.module_list:
             batch_dict = cur_module(batch_dict)
+        if self.training:
+            loss, tb_dict, disp_dict = self.get_training_loss()
+            return {'loss': loss}, tb_dict, disp_dict
         return self.post_processing(batch_dict)
 
-    def get_training_loss(self):
-        raise NotImplementedError("PointRCNN.get_training_loss: " + TRAINING_ROW)
+    def get_training_loss(self, as_tensors=False):
+        """-> (loss_point + loss_rcnn, tb_dict, disp_dict): the tb_dict of both heads -- 'point_loss_cls',
+        'point_pos_num', 'point_loss_box', 'rcnn_loss_cls', 'rcnn_loss_reg', 'rcnn_loss_corner', 'rcnn_loss' -- as Python
+        floats read with one copy, or 0-dim device tensors with as_tensors=True."""
+        if not self.trainable:
+            raise NotImplementedError("PointRCNN.get_training_loss: " + TRAINING_ROW)
+        loss_point, tb_dict = self.point_head.get_loss(as_tensors=True)
+        loss_rcnn, tb_dict = self.roi_head.get_loss(tb_dict, as_tensors=True)
+        return loss_point + loss_rcnn, (tb_dict if as_tensors else host_values(tb_dict)), {}
 
     def select_predictions(self, batch_dict):
         """The detector's post-processing without the recall record, for the whole batch in one chain: batch_box_preds

@@ -9,16 +9,28 @@ cls_layers.*, reg_layers.*).  The inference half:
                    the concatenation, the pooling op and the five torch ops around it;
   forward          in eval mode; generate_predicted_boxes; init_weights.
 
-forward in training mode is the training row (not built) and raises NotImplementedError."""
+The training half is built only with trainable=True; without it forward in training mode,
+assign_targets and get_loss raise NotImplementedError as before.  With it: the proposals with NMS_CONFIG.TRAIN, the
+ProposalTargetLayer (two launches for the batch: proposal_target_layer.py), the canonical transform of the sampled
+ground truth, the pooling and the second stage on the sampled RoIs, and the reference's two losses written as masked
+sums over all ROI_PER_IMAGE rows (torch.where, not a product with zero) instead of `[fg_mask]` indexing and the
+`fg_sum > 0` branch on the host: the same values and gradients without a host-sized shape.  The loss function and the
+target layer have no parameters or buffers: the state dict is the same.  get_loss reads the device once for its tb_dict
+(never with as_tensors=True); 'rcnn_loss_corner' is always present (0 without a foreground RoI, where the reference
+leaves the key out)."""
+import math
+
 import torch
 import torch.nn as nn
+import torch.nn.functional as F
 
 from .. import roipoint_ops
-from . import box_coder_utils, pointnet2_modules
+from . import box_coder_utils, loss_utils, pointnet2_modules
 from .base_bev_backbone import _get
 from .box_utils import rotate_points_along_z
 from .model_nms_utils import class_agnostic_nms
-from .point_head_box import TRAINING_ROW
+from .point_head_box import TRAINING_ROW, host_values
+from .proposal_target_layer import ProposalTargetLayer
 
 
 def _as_dict(cfg):
@@ -37,10 +49,15 @@ def _pointwise(channels, bias, norm, conv=nn.Conv2d):
 
 
 class PointRCNNHead(nn.Module):
-    def __init__(self, input_channels, model_cfg, num_class=1, **kwargs):
+    def __init__(self, input_channels, model_cfg, num_class=1, trainable=False, **kwargs):
         super().__init__()
         self.model_cfg, self.num_class, self.forward_ret_dict = model_cfg, num_class, None
+        self.trainable = bool(trainable)
         target_cfg = _get(model_cfg, 'TARGET_CONFIG')
+        if self.trainable:
+            self.proposal_target_layer = ProposalTargetLayer(roi_sampler_cfg=target_cfg)
+            self.reg_loss_func = loss_utils.WeightedSmoothL1Loss(
+                code_weights=_get(_get(model_cfg, 'LOSS_CONFIG'), 'LOSS_WEIGHTS')['code_weights'])
         self.box_coder = getattr(box_coder_utils, _get(target_cfg, 'BOX_CODER'))(
             **_as_dict(_get(target_cfg, 'BOX_CODER_CONFIG', {})))
         use_bn = bool(_get(model_cfg, 'USE_BN'))
@@ -133,11 +150,106 @@ class PointRCNNHead(nn.Module):
                 _get(cfg, 'POOL_EXTRA_WIDTH'), _get(cfg, 'NUM_SAMPLED_POINTS'), _get(cfg, 'DEPTH_NORMALIZER'),
                 return_idx=return_idx)
 
-    def assign_targets(self, batch_dict):
-        raise NotImplementedError("PointRCNNHead.assign_targets: " + TRAINING_ROW)
+    def assign_targets(self, batch_dict, sampled_inds=None):
+        """rois, roi_scores, roi_labels, gt_boxes (B, G, 8) with G >= 1 (a batch without any box is padded to one all-zero
+        row; G = 0 raises Dfu3dError) of the batch; sampled_inds (B, ROI_PER_IMAGE) given: no draw -> the target layer's dict with 'gt_of_rois_src' (the
+        sampled ground truth as it is) and 'gt_of_rois' in the frame of its RoI: the centre moved to the RoI's, turned
+        by -roi_ry, the heading difference folded into [-pi/2, pi/2] (a box facing the other way counts as aligned)."""
+        if not self.trainable:
+            raise NotImplementedError("PointRCNNHead.assign_targets: " + TRAINING_ROW)
+        batch_size = batch_dict['batch_size']
+        targets = self.proposal_target_layer(batch_dict, sampled_inds=sampled_inds)
+        rois, gt = targets['rois'], targets['gt_of_rois']
+        targets['gt_of_rois_src'] = gt.clone().detach()
+        two_pi = 2 * math.pi
+        roi_ry = rois[:, :, 6] % two_pi
+        gt[:, :, 0:3] = gt[:, :, 0:3] - rois[:, :, 0:3]
+        gt[:, :, 6] = gt[:, :, 6] - roi_ry
+        gt = rotate_points_along_z(gt.view(-1, 1, gt.shape[-1]), -roi_ry.view(-1)).view(batch_size, -1, gt.shape[-1])
+        heading = gt[:, :, 6] % two_pi                                     # 0 .. 2 pi
+        opposite = (heading > math.pi * 0.5) & (heading < math.pi * 1.5)
+        heading = torch.where(opposite, (heading + math.pi) % two_pi, heading)        # 0 .. pi/2 or 3 pi/2 .. 2 pi
+        heading = torch.where(heading > math.pi, heading - math.pi * 2, heading)      # -pi/2 .. pi/2
+        gt[:, :, 6] = torch.clamp(heading, min=-math.pi / 2, max=math.pi / 2)
+        targets['gt_of_rois'] = gt
+        return targets
 
-    def get_loss(self, tb_dict=None):
-        raise NotImplementedError("PointRCNNHead.get_loss: " + TRAINING_ROW)
+    def _need_targets(self, what):
+        if not self.trainable:
+            raise NotImplementedError("PointRCNNHead.%s: %s" % (what, TRAINING_ROW))
+        if not self.forward_ret_dict or 'rcnn_cls_labels' not in self.forward_ret_dict:
+            raise RuntimeError("PointRCNNHead.%s: no targets -- run forward in training mode on a batch with gt_boxes first" % what)
+        return self.forward_ret_dict
+
+    def get_box_cls_layer_loss(self, forward_ret_dict):
+        """The (binary) cross entropy of every sampled RoI whose label is not -1, their mean -> (loss, {'rcnn_loss_cls'})."""
+        cfg = _get(self.model_cfg, 'LOSS_CONFIG')
+        rcnn_cls, labels = forward_ret_dict['rcnn_cls'], forward_ret_dict['rcnn_cls_labels'].view(-1)
+        kind = _get(cfg, 'CLS_LOSS')
+        if kind == 'BinaryCrossEntropy':
+            # an ignored RoI (-1) gets the target 0 and is masked below: binary_cross_entropy refuses targets outside [0, 1]
+            each = F.binary_cross_entropy(torch.sigmoid(rcnn_cls.view(-1)), labels.clamp(min=0).float(), reduction='none')
+        elif kind == 'CrossEntropy':
+            each = F.cross_entropy(rcnn_cls, labels, reduction='none', ignore_index=-1)
+        else:
+            raise NotImplementedError("PointRCNNHead: CLS_LOSS %r" % (kind,))
+        valid = labels >= 0
+        loss = torch.where(valid, each, torch.zeros_like(each)).sum() / torch.clamp(valid.float().sum(), min=1.0)
+        loss = loss * _get(cfg, 'LOSS_WEIGHTS')['rcnn_cls_weight']
+        return loss, {'rcnn_loss_cls': loss.detach()}
+
+    def get_box_reg_layer_loss(self, forward_ret_dict):
+        """Over the RoIs with reg_valid_mask: the smooth L1 of the box code against the ResidualCoder code of the
+        canonical ground truth (the RoI at the origin with heading 0 as the anchor), summed and divided by their number,
+        plus the mean corner loss of the decoded boxes against the ground truth as it is -> (loss, {'rcnn_loss_reg' --
+        without the corner term, as the reference records it --, 'rcnn_loss_corner'})."""
+        cfg = _get(self.model_cfg, 'LOSS_CONFIG')
+        weights = _get(cfg, 'LOSS_WEIGHTS')
+        if _get(cfg, 'REG_LOSS') != 'smooth-l1':
+            raise NotImplementedError("PointRCNNHead: REG_LOSS %r" % (_get(cfg, 'REG_LOSS'),))
+        code_size = self.box_coder.code_size
+        fg = forward_ret_dict['reg_valid_mask'].view(-1) > 0
+        gt_ct = forward_ret_dict['gt_of_rois'][..., 0:code_size]
+        gt_src = forward_ret_dict['gt_of_rois_src'][..., 0:code_size].reshape(-1, code_size)
+        rois = forward_ret_dict['rois']
+        rows = gt_ct.reshape(-1, code_size).shape[0]
+        rcnn_reg = forward_ret_dict['rcnn_reg'].view(rows, -1)
+        fg_sum = torch.clamp(fg.float().sum(), min=1.0)
+        anchors = rois.clone().detach().view(-1, code_size)
+        anchors[:, 0:3] = 0
+        anchors[:, 6] = 0
+        reg_targets = self.box_coder.encode_torch(gt_ct.reshape(rows, code_size), anchors)
+        each = self.reg_loss_func(rcnn_reg.unsqueeze(dim=0), reg_targets.unsqueeze(dim=0)).view(rows, -1)
+        loss_reg = torch.where(fg[:, None], each, torch.zeros_like(each)).sum() / fg_sum
+        loss_reg = loss_reg * weights['rcnn_reg_weight']
+        tb_dict = {'rcnn_loss_reg': loss_reg.detach()}
+        corner = loss_reg.new_zeros(())
+        if _get(cfg, 'CORNER_LOSS_REGULARIZATION'):
+            # a row without a target decodes zeros (its own RoI): finite whatever the head predicts, and no gradient
+            codes = torch.where(fg[:, None], rcnn_reg, torch.zeros_like(rcnn_reg))
+            flat = rois.reshape(-1, code_size)
+            at_origin = flat.clone().detach()
+            at_origin[:, 0:3] = 0
+            boxes = self.box_coder.decode_torch(codes.view(1, rows, code_size), at_origin.view(1, rows, code_size))
+            boxes = rotate_points_along_z(boxes.view(-1, 1, code_size), flat[:, 6]).squeeze(dim=1)
+            boxes = torch.cat((boxes[:, 0:3] + flat[:, 0:3], boxes[:, 3:]), dim=-1)
+            each = loss_utils.get_corner_loss_lidar(boxes[:, 0:7], gt_src[:, 0:7])
+            corner = torch.where(fg, each, torch.zeros_like(each)).sum() / fg_sum
+            corner = corner * weights['rcnn_corner_weight']
+        tb_dict['rcnn_loss_corner'] = corner.detach()
+        return loss_reg + corner, tb_dict
+
+    def get_loss(self, tb_dict=None, as_tensors=False):
+        """-> (rcnn_loss, tb_dict): 'rcnn_loss_cls', 'rcnn_loss_reg', 'rcnn_loss_corner', 'rcnn_loss' as Python floats
+        read with ONE copy, or with as_tensors=True as 0-dim device tensors without any synchronisation."""
+        ret = self._need_targets('get_loss')
+        tb_dict = {} if tb_dict is None else tb_dict
+        loss_cls, own = self.get_box_cls_layer_loss(ret)
+        loss_reg, more = self.get_box_reg_layer_loss(ret)
+        loss = loss_cls + loss_reg
+        own = dict(own, **more, rcnn_loss=loss.detach())
+        tb_dict.update(own if as_tensors else host_values(own))
+        return loss, tb_dict
 
     def generate_predicted_boxes(self, batch_size, rois, cls_preds, box_preds):
         """rois (B, M, 7), cls_preds (B * M, num_class), box_preds (B * M, code_size) -> batch_cls_preds (B, M, .),
@@ -165,9 +277,16 @@ class PointRCNNHead(nn.Module):
         return flat(self.cls_layers), flat(self.reg_layers)
 
     def forward(self, batch_dict):
-        if self.training:
+        if self.training and not self.trainable:
             raise NotImplementedError("PointRCNNHead.forward in training mode: " + TRAINING_ROW)
-        self.proposal_layer(batch_dict, nms_config=_get(_get(self.model_cfg, 'NMS_CONFIG'), 'TEST'))
+        self.proposal_layer(batch_dict, nms_config=_get(_get(self.model_cfg, 'NMS_CONFIG'), 'TRAIN' if self.training else 'TEST'))
+        if self.training:
+            targets = self.assign_targets(batch_dict)
+            batch_dict['rois'], batch_dict['roi_labels'] = targets['rois'], targets['roi_labels']
+            rcnn_cls, rcnn_reg = self.second_stage(self.roipool3d_gpu(batch_dict))
+            targets.update(rcnn_cls=rcnn_cls, rcnn_reg=rcnn_reg)
+            self.forward_ret_dict = targets
+            return batch_dict
         rcnn_cls, rcnn_reg = self.second_stage(self.roipool3d_gpu(batch_dict))
         cls_preds, box_preds = self.generate_predicted_boxes(batch_dict['batch_size'], batch_dict['rois'], rcnn_cls, rcnn_reg)
         batch_dict.update(rcnn_cls=rcnn_cls, rcnn_reg=rcnn_reg, batch_cls_preds=cls_preds, batch_box_preds=box_preds,
