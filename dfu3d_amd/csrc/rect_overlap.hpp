@@ -33,12 +33,19 @@ __device__ __forceinline__ Rect make_rect(const float *b, int fmt) {
 
 __device__ __forceinline__ float rect_area(const Rect &r) { return 4.0f * r.hu * r.hv; }
 
-// Area of A n B.  pu / pv: this thread's column of the two [MAXV][IB] LDS planes (ping) and qu / qv (pong).
-__device__ inline float overlap_area(const Rect &A, const Rect &B, float *pu, float *pv, float *qu, float *qv) {
+// The circumscribed circles of A and B are apart: overlap_area's first test, which returns 0 for such a pair without
+// touching LDS.  A caller that sorts pairs by it before calling overlap_area gets overlap_area's own answer.
+__device__ __forceinline__ bool circles_apart(const Rect &A, const Rect &B) {
   const float dx = A.cx - B.cx, dy = A.cy - B.cy;
   const float ra2 = A.hu * A.hu + A.hv * A.hv, rb2 = B.hu * B.hu + B.hv * B.hv;
   const float rr = ra2 + rb2 + 2.0f * sqrtf(ra2 * rb2);              // (ra + rb)^2
-  if (dx * dx + dy * dy > rr) return 0.0f;                            // circumscribed circles apart
+  return dx * dx + dy * dy > rr;
+}
+
+// Area of A n B.  pu / pv: this thread's column of the two [MAXV][IB] LDS planes (ping) and qu / qv (pong).
+__device__ inline float overlap_area(const Rect &A, const Rect &B, float *pu, float *pv, float *qu, float *qv) {
+  if (circles_apart(A, B)) return 0.0f;
+  const float dx = A.cx - B.cx, dy = A.cy - B.cy;
   // A's centre and axes in B's frame
   const float cu = dx * B.ax + dy * B.ay, cv = -dx * B.ay + dy * B.ax;
   const float eu = A.ax * B.ax + A.ay * B.ay, ev = -A.ax * B.ay + A.ay * B.ax;     // A's first axis

@@ -39,11 +39,13 @@ def _module_class(model_cfg, section):
 
 
 class PointRCNN(nn.Module):
-    def __init__(self, model_cfg, num_class, dataset=None, trainable=False, **kwargs):
+    def __init__(self, model_cfg, num_class, dataset=None, trainable=False, batched_proposals=False, **kwargs):
         """dataset: an object with class_names and point_feature_encoder.num_point_features -- or the same as keywords
-        (num_point_features for the last).  trainable: build the training half of both heads."""
+        (num_point_features for the last).  trainable: build the training half of both heads.  batched_proposals: the
+        RoI head's proposal stage for the whole batch at once (PointRCNNHead.proposal_layer_batched)."""
         super().__init__()
         self.trainable = bool(trainable)
+        self.batched_proposals = bool(batched_proposals)
         if dataset is None:
             feats = kwargs.pop('num_point_features')
             dataset = _Dataset(point_feature_encoder=_Dataset(num_point_features=feats), **kwargs)
@@ -67,7 +69,8 @@ class PointRCNN(nn.Module):
                               trainable=self.trainable)
         cfg, cls = _module_class(model_cfg, 'ROI_HEAD')
         self.roi_head = cls(model_cfg=cfg, input_channels=num_point_features,
-                            num_class=num_class if not _get(cfg, 'CLASS_AGNOSTIC', False) else 1, trainable=self.trainable)
+                            num_class=num_class if not _get(cfg, 'CLASS_AGNOSTIC', False) else 1, trainable=self.trainable,
+                            batched_proposals=self.batched_proposals)
         self.module_list = [self.backbone_3d, self.point_head, self.roi_head]
 
     @property

@@ -5,6 +5,9 @@ cls_layers.*, reg_layers.*).  The inference half:
   proposal_layer   the first stage's stacked predictions viewed as (B, N, .) -- the backbone has checked on the device that
                    the samples have equal sizes, so no `batch_index == index` mask is built -- and the existing
                    class_agnostic_nms per sample (NMS_PRE_MAXSIZE = 9000 is beyond the segmented NMS's cap);
+  proposal_layer_batched  the same stage for the whole batch in proposal_ops.LAUNCHES launches and without a host read
+                   (proposal_ops.proposals: csrc/proposal_stage.hip); taken by forward only with
+                   batched_proposals=True.  Equal scores are ordered by point index there, by torch.topk here;
   roipool3d_gpu    ONE call of the fused RoI-point pooling (roipoint_ops.pool_fused: csrc/roipoint_stage.hip) instead of
                    the concatenation, the pooling op and the five torch ops around it;
   forward          in eval mode; generate_predicted_boxes; init_weights.
@@ -24,7 +27,7 @@ import torch
 import torch.nn as nn
 import torch.nn.functional as F
 
-from .. import roipoint_ops
+from .. import proposal_ops, roipoint_ops
 from . import box_coder_utils, loss_utils, pointnet2_modules
 from .base_bev_backbone import _get
 from .box_utils import rotate_points_along_z
@@ -49,10 +52,11 @@ def _pointwise(channels, bias, norm, conv=nn.Conv2d):
 
 
 class PointRCNNHead(nn.Module):
-    def __init__(self, input_channels, model_cfg, num_class=1, trainable=False, **kwargs):
+    def __init__(self, input_channels, model_cfg, num_class=1, trainable=False, batched_proposals=False, **kwargs):
         super().__init__()
         self.model_cfg, self.num_class, self.forward_ret_dict = model_cfg, num_class, None
         self.trainable = bool(trainable)
+        self.batched_proposals = bool(batched_proposals)
         target_cfg = _get(model_cfg, 'TARGET_CONFIG')
         if self.trainable:
             self.proposal_target_layer = ProposalTargetLayer(roi_sampler_cfg=target_cfg)
@@ -135,6 +139,38 @@ class PointRCNNHead(nn.Module):
         batch_dict['roi_scores'] = roi_scores
         batch_dict['roi_labels'] = roi_labels + 1
         batch_dict['roi_point_idx'] = roi_point_idx
+        batch_dict['has_class_labels'] = cls_preds.shape[-1] > 1
+        batch_dict.pop('batch_index', None)
+        return batch_dict
+
+    @torch.no_grad()
+    def proposal_layer_batched(self, batch_dict, nms_config):
+        """proposal_layer for the whole batch at once: the same keys with the same meaning, plus 'num_rois' int32 (B), the
+        survivors of every sample.  No host read.  Scores and labels are those of one torch.max(cls_preds, dim=2); among
+        equal scores the lower point index comes first (proposal_layer leaves them to torch.topk)."""
+        if batch_dict.get('rois', None) is not None:
+            return batch_dict
+        if _get(nms_config, 'MULTI_CLASSES_NMS'):
+            raise NotImplementedError("PointRCNNHead.proposal_layer_batched: MULTI_CLASSES_NMS")
+        if _get(nms_config, 'NMS_TYPE') != 'nms_gpu':
+            raise NotImplementedError("PointRCNNHead.proposal_layer_batched: NMS_TYPE %r" % (_get(nms_config, 'NMS_TYPE'),))
+        batch_size = batch_dict['batch_size']
+        box_preds, cls_preds = batch_dict['batch_box_preds'], batch_dict['batch_cls_preds']
+        if box_preds.dim() == 2:
+            if box_preds.shape[0] % batch_size:
+                raise ValueError("proposal_layer_batched: %d predictions are not %d samples of equal size"
+                                 % (box_preds.shape[0], batch_size))
+            box_preds = box_preds.view(batch_size, -1, box_preds.shape[-1])
+            cls_preds = cls_preds.view(batch_size, -1, cls_preds.shape[-1])
+        all_scores, all_labels = torch.max(cls_preds, dim=2)
+        rois, roi_scores, roi_labels, roi_point_idx, num_rois = proposal_ops.proposals(
+            all_scores.float().contiguous(), all_labels.contiguous(), box_preds.float().contiguous(),
+            _get(nms_config, 'NMS_THRESH'), _get(nms_config, 'NMS_PRE_MAXSIZE'), _get(nms_config, 'NMS_POST_MAXSIZE'))
+        batch_dict['rois'] = rois
+        batch_dict['roi_scores'] = roi_scores
+        batch_dict['roi_labels'] = roi_labels
+        batch_dict['roi_point_idx'] = roi_point_idx
+        batch_dict['num_rois'] = num_rois
         batch_dict['has_class_labels'] = cls_preds.shape[-1] > 1
         batch_dict.pop('batch_index', None)
         return batch_dict
@@ -279,7 +315,8 @@ class PointRCNNHead(nn.Module):
     def forward(self, batch_dict):
         if self.training and not self.trainable:
             raise NotImplementedError("PointRCNNHead.forward in training mode: " + TRAINING_ROW)
-        self.proposal_layer(batch_dict, nms_config=_get(_get(self.model_cfg, 'NMS_CONFIG'), 'TRAIN' if self.training else 'TEST'))
+        propose = self.proposal_layer_batched if self.batched_proposals else self.proposal_layer
+        propose(batch_dict, nms_config=_get(_get(self.model_cfg, 'NMS_CONFIG'), 'TRAIN' if self.training else 'TEST'))
         if self.training:
             targets = self.assign_targets(batch_dict)
             batch_dict['rois'], batch_dict['roi_labels'] = targets['rois'], targets['roi_labels']
