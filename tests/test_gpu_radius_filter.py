@@ -25,8 +25,13 @@ def _t(a):
     return torch.as_tensor(np.ascontiguousarray(a)).to(DEV).contiguous()
 
 
-def _joint_filter_then_fuse_equals_oracle(st, segsA, segsB, ra, rb):
-    """-> the number of instances whose fuse was skipped because the filter emptied a list"""
+def _zeros(n, dtype):
+    return torch.zeros(n, dtype=dtype, device=DEV)
+
+
+def _joint_filter_then_fuse_equals_oracle(st, segsA, segsB, ra, rb, alloc=_zeros):
+    """-> the number of instances whose fuse was skipped because the filter emptied a list.
+    alloc: the three scratch buffers (tests/test_gpu_guard_bands.py passes poisoned, guarded memory)."""
     S = len(segsA)
     chunks, base_a, base_b, cur = [], [], [], 0
     for a, b in zip(segsA, segsB):
@@ -42,9 +47,9 @@ def _joint_filter_then_fuse_equals_oracle(st, segsA, segsB, ra, rb):
     ta, tb = _t(np.array(base_a, np.int64)), _t(np.array(base_b, np.int64))
     # the joint table, as dfu3d_segments_build lays it out: s < S the A lists, S + s the B lists
     base_ab = torch.cat([ta, tb]); cnt_ab = torch.cat([cnt_a, cnt_b]); rad_ab = _t(np.concatenate([ra, rb]))
-    tile_off = torch.zeros(2 * S + 2, dtype=torch.int32, device=DEV)
-    flags = torch.zeros(cap, dtype=torch.uint8, device=DEV)
-    queue = torch.zeros(st.rf_queue_ints(cap), dtype=torch.int32, device=DEV)
+    tile_off = alloc(2 * S + 2, torch.int32)
+    flags = alloc(cap, torch.uint8)
+    queue = alloc(st.rf_queue_ints(cap), torch.int32)
     st.radius_filter(px, py, pz, base_ab, cnt_ab, rad_ab, 1, 2 * S, cap, tile_off, flags, queue,
                      phases=st.RF_ALL & ~st.RF_COMPACT)
     st.ballquery_fuse(px, py, pz, ta, cnt_a, tb, cnt_b, 0.1, S, cap, tile_off, flags, masked="joint")

@@ -31,6 +31,12 @@ def _t(a, dtype=None):
     return t.to(DEV).contiguous()
 
 
+def _zeros(n, dtype):
+    """Scratch and outputs as these tests make them: zero-filled.  The runners below take the allocator as `alloc`;
+    tests/test_gpu_guard_bands.py passes one that hands out poisoned, guarded memory (torch.empty under its mode)."""
+    return torch.zeros(n, dtype=dtype, device=DEV)
+
+
 def _rand_calib(rng, yaw_deg=0.0, H=900, W=1600):
     from dfu3d_amd import synth
     return synth.make_calibration(yaw_deg, H, W, rng)
@@ -90,11 +96,7 @@ def test_fp32_backprojection_bound_holds_on_this_device(st):
 
 
 # ------------------------------------------------------------------ a9
-def test_segments_build_orders_every_list_across_chunks_and_waves(st):
-    """Per-view bit sets -> per-instance ordered lists (my_loader.py:547-565 semantics: an item belongs to every instance
-    whose bit it carries, lists keep the item order, LiDAR list directly followed by the pseudo list).  Item counts sit
-    on the kernel's granularities (64-item ballots, 256-item wave ranges, 2048-item steps, 32768-item chunks) and next
-    to them; the float32 shadow and the joint 2S table are checked too."""
+def _segments_case():
     rng = np.random.default_rng(33)
     M = 6
     a_ns = [0, 1, 63, 64, 65, 255, 2049, 5000]
@@ -117,24 +119,46 @@ def test_segments_build_orders_every_list_across_chunks_and_waves(st):
     S = V * M
     total = sum(int(((abits[v, :a_ns[v]] >> j) & 1).sum() + ((bbits[v, :b_ns[v]] >> j) & 1).sum()) for v in range(V) for j in range(M))
     cap = total + 64
+    rad = rng.uniform(0.3, 3.0, S), rng.uniform(0.3, 3.0, S)
+    return dict(M=M, V=V, S=S, a_ns=a_ns, b_ns=b_ns, a_cap=a_cap, b_cap=b_cap, abits=abits, axyz=axyz, bbits=bbits, bxyz=bxyz,
+                total=total, cap=cap, rad=rad)
+
+
+def _segments_run(st, c, alloc=None):
+    """alloc=None: the pool pre-filled with 7.0 and zeroed tables, as this file's test makes them."""
+    V, M, S, cap, a_cap, b_cap = c["V"], c["M"], c["S"], c["cap"], c["a_cap"], c["b_cap"]
+    abits, axyz, bbits, bxyz = c["abits"], c["axyz"], c["bbits"], c["bxyz"]
     dev = DEV
     t = lambda a, dt=None: torch.as_tensor(np.ascontiguousarray(a)).to(dev) if dt is None else torch.as_tensor(np.ascontiguousarray(a)).to(dev).to(dt)
-    px, py, pz = (torch.full((cap,), 7.0, dtype=torch.float64, device=dev) for _ in range(3))
-    base_a, base_b = torch.zeros(S, dtype=torch.int64, device=dev), torch.zeros(S, dtype=torch.int64, device=dev)
-    cnt_a, cnt_b = torch.zeros(S, dtype=torch.int32, device=dev), torch.zeros(S, dtype=torch.int32, device=dev)
+    if alloc is None:
+        px, py, pz = (torch.full((cap,), 7.0, dtype=torch.float64, device=dev) for _ in range(3))
+        alloc = _zeros
+    else:
+        px, py, pz = (alloc(cap, torch.float64) for _ in range(3))
+    base_a, base_b = alloc(S, torch.int64), alloc(S, torch.int64)
+    cnt_a, cnt_b = alloc(S, torch.int32), alloc(S, torch.int32)
     cursor = torch.zeros(1, dtype=torch.int64, device=dev)
     status = torch.zeros(1, dtype=torch.int32, device=dev)
-    rad_a = t(rng.uniform(0.3, 3.0, S)); rad_b = t(rng.uniform(0.3, 3.0, S))
-    shadow = torch.zeros(st.shadow_floats(cap), dtype=torch.float32, device=dev)
-    base_ab = torch.zeros(2 * S, dtype=torch.int64, device=dev)
-    cnt_ab = torch.zeros(2 * S, dtype=torch.int32, device=dev)
-    rad_ab = torch.zeros(2 * S, dtype=torch.float64, device=dev)
+    rad_a = t(c["rad"][0]); rad_b = t(c["rad"][1])
+    shadow = alloc(st.shadow_floats(cap), torch.float32)
+    base_ab = alloc(2 * S, torch.int64)
+    cnt_ab = alloc(2 * S, torch.int32)
+    rad_ab = alloc(2 * S, torch.float64)
     st.segments_build(t(abits.reshape(-1)), t(axyz[..., 0].reshape(-1)), t(axyz[..., 1].reshape(-1)), t(axyz[..., 2].reshape(-1)),
-                      t(np.array(a_ns, np.int32)), a_cap,
+                      t(np.array(c["a_ns"], np.int32)), a_cap,
                       t(bbits.reshape(-1)), t(bxyz[..., 0].reshape(-1)), t(bxyz[..., 1].reshape(-1)), t(bxyz[..., 2].reshape(-1)),
-                      t(np.array(b_ns, np.int32)), b_cap, V, M, cap, cursor, px, py, pz, base_a, cnt_a, base_b, cnt_b, status,
+                      t(np.array(c["b_ns"], np.int32)), b_cap, V, M, cap, cursor, px, py, pz, base_a, cnt_a, base_b, cnt_b, status,
                       rad_a=rad_a, rad_b=rad_b, shadow=shadow, base_ab=base_ab, cnt_ab=cnt_ab, rad_ab=rad_ab)
     torch.cuda.synchronize()
+    return dict(status=status, cursor=cursor, px=px, py=py, pz=pz, shadow=shadow, base_a=base_a, cnt_a=cnt_a, base_b=base_b,
+                cnt_b=cnt_b, base_ab=base_ab, cnt_ab=cnt_ab, rad_ab=rad_ab)
+
+
+def _segments_verify(c, o):
+    V, M, S, cap, total = c["V"], c["M"], c["S"], c["cap"], c["total"]
+    a_ns, b_ns, abits, axyz, bbits, bxyz = c["a_ns"], c["b_ns"], c["abits"], c["axyz"], c["bbits"], c["bxyz"]
+    status, cursor, px, py, pz, shadow = o["status"], o["cursor"], o["px"], o["py"], o["pz"], o["shadow"]
+    base_a, cnt_a, base_b, cnt_b, base_ab, cnt_ab = o["base_a"], o["cnt_a"], o["base_b"], o["cnt_b"], o["base_ab"], o["cnt_ab"]
     assert int(status.item()) == 0 and int(cursor.item()) == total
     P = torch.stack([px, py, pz], 1).cpu().numpy()
     sh = shadow[:4 * cap].view(-1, 4).cpu().numpy()
@@ -155,8 +179,33 @@ def test_segments_build_orders_every_list_across_chunks_and_waves(st):
             run += len(ea) + len(eb)
 
 
+def test_segments_build_orders_every_list_across_chunks_and_waves(st):
+    """Per-view bit sets -> per-instance ordered lists (my_loader.py:547-565 semantics: an item belongs to every instance
+    whose bit it carries, lists keep the item order, LiDAR list directly followed by the pseudo list).  Item counts sit
+    on the kernel's granularities (64-item ballots, 256-item wave ranges, 2048-item steps, 32768-item chunks) and next
+    to them; the float32 shadow and the joint 2S table are checked too."""
+    c = _segments_case()
+    _segments_verify(c, _segments_run(st, c))
+
+
 # ------------------------------------------------------------------ a10
-def test_radius_filter_matches_oracle(st):
+def _radius_filter_run(st, segs, radius, nb, alloc=_zeros):
+    """One dfu3d_radius_filter call (every phase) over the segments -> (segment bases, counts after, pool after)."""
+    P, base, cnt, cap = _pool_from_segments(segs)
+    px, py, pz = _t(P[:, 0]), _t(P[:, 1]), _t(P[:, 2])
+    S = len(segs)
+    seg_cnt = _t(cnt)
+    st.radius_filter(px, py, pz, _t(base), seg_cnt, _t(radius), nb, S, cap,
+                     alloc(S + 1, torch.int32),
+                     alloc(cap, torch.uint8),
+                     alloc(st.rf_queue_ints(cap), torch.int32))
+    torch.cuda.synchronize()
+    out_cnt = seg_cnt.cpu().numpy()
+    X = torch.stack([px, py, pz], 1).cpu().numpy()
+    return base, out_cnt, X
+
+
+def _radius_filter_cases():
     rng = np.random.default_rng(10)
     sizes = [0, 1, 2, 5, 63, 64, 65, 255, 256, 257, 700, 1024, 1025, 3000, 5200]
     segs = [_clustered_points(rng, n) for n in sizes]
@@ -164,28 +213,27 @@ def test_radius_filter_matches_oracle(st):
     radius = np.array([3.0, 0.6] * 8)[:len(segs)]
     radius[3] = -1.0                                                   # H4: drop all
     radius[4] = 0.0                                                    # H5: keep all
+    return segs, radius
+
+
+def _radius_filter_verify(segs, radius, nb, base, out_cnt, X):
+    for s, pts in enumerate(segs):
+        if radius[s] < 0:
+            keep = np.zeros((0,), np.int64)
+        elif radius[s] == 0:
+            keep = np.arange(len(pts))
+        else:
+            keep = O.radius_outlier(pts, nb, radius[s])
+        assert out_cnt[s] == len(keep), (s, nb, out_cnt[s], len(keep))
+        got = X[base[s]:base[s] + out_cnt[s]]
+        assert np.array_equal(got, pts[keep]), (s, nb)
+
+
+def test_radius_filter_matches_oracle(st):
+    segs, radius = _radius_filter_cases()
     for nb in (1, 4):
-        P, base, cnt, cap = _pool_from_segments(segs)
-        px, py, pz = _t(P[:, 0]), _t(P[:, 1]), _t(P[:, 2])
-        S = len(segs)
-        seg_cnt = _t(cnt)
-        st.radius_filter(px, py, pz, _t(base), seg_cnt, _t(radius), nb, S, cap,
-                         torch.zeros(S + 1, dtype=torch.int32, device=DEV),
-                         torch.zeros(cap, dtype=torch.uint8, device=DEV),
-                         torch.zeros(st.rf_queue_ints(cap), dtype=torch.int32, device=DEV))
-        torch.cuda.synchronize()
-        out_cnt = seg_cnt.cpu().numpy()
-        X = torch.stack([px, py, pz], 1).cpu().numpy()
-        for s, pts in enumerate(segs):
-            if radius[s] < 0:
-                keep = np.zeros((0,), np.int64)
-            elif radius[s] == 0:
-                keep = np.arange(len(pts))
-            else:
-                keep = O.radius_outlier(pts, nb, radius[s])
-            assert out_cnt[s] == len(keep), (s, nb, out_cnt[s], len(keep))
-            got = X[base[s]:base[s] + out_cnt[s]]
-            assert np.array_equal(got, pts[keep]), (s, nb)
+        base, out_cnt, X = _radius_filter_run(st, segs, radius, nb)
+        _radius_filter_verify(segs, radius, nb, base, out_cnt, X)
 
 
 def test_radius_filter_pairs_at_the_threshold(st):
@@ -209,17 +257,7 @@ def test_radius_filter_pairs_at_the_threshold(st):
             radius.append(r)
     radius = np.array(radius)
     for nb in (1,):
-        P, base, cnt, cap = _pool_from_segments(segs)
-        px, py, pz = _t(P[:, 0]), _t(P[:, 1]), _t(P[:, 2])
-        S = len(segs)
-        seg_cnt = _t(cnt)
-        st.radius_filter(px, py, pz, _t(base), seg_cnt, _t(radius), nb, S, cap,
-                         torch.zeros(S + 1, dtype=torch.int32, device=DEV),
-                         torch.zeros(cap, dtype=torch.uint8, device=DEV),
-                         torch.zeros(st.rf_queue_ints(cap), dtype=torch.int32, device=DEV))
-        torch.cuda.synchronize()
-        out_cnt = seg_cnt.cpu().numpy()
-        X = torch.stack([px, py, pz], 1).cpu().numpy()
+        base, out_cnt, X = _radius_filter_run(st, segs, radius, nb)
         n_kept = n_drop = 0
         for s, pts in enumerate(segs):
             keep = O.radius_outlier(pts, nb, radius[s])
@@ -231,9 +269,8 @@ def test_radius_filter_pairs_at_the_threshold(st):
 
 
 # ------------------------------------------------------------------ a12
-def test_ballquery_fuse_matches_oracle(st):
-    rng = np.random.default_rng(12)
-    cases = [(0, 10), (10, 0), (40, 300), (1, 50), (1500, 2600), (3, 3), (4500, 900), (4096, 5000)]
+def _fuse_segments(seed, cases, far=False):
+    rng = np.random.default_rng(seed)
     segsA, segsB = [], []
     for na, nb in cases:
         a = rng.normal(0, 2.0, (na, 3))
@@ -241,8 +278,17 @@ def test_ballquery_fuse_matches_oracle(st):
         if na and nb:
             h = nb // 2
             b[:h] = a[rng.integers(0, na, h)] + rng.normal(0, 0.06, (h, 3))
+            if far:
+                far_ = rng.random(nb) < 0.2                         # isolated pseudo points: the filter drops them
+                b[far_] = rng.uniform(-300, 300, (int(far_.sum()), 3))
         segsA.append(a)
         segsB.append(b)
+    return segsA, segsB
+
+
+def _ballquery_fuse_run(st, segsA, segsB, radius=None, alloc=_zeros):
+    """dfu3d_ballquery_fuse over the pool A_s | B_s; with `radius`, the radius filter of the B lists without its
+    compaction first and then dfu3d_ballquery_fuse_masked.  -> (A bases, B counts after, B bases after, pool after)."""
     # pool layout: A_s then B_s adjacent (as dfu3d_segments_build lays them out)
     chunks, base_a, base_b, cur = [], [], [], 0
     for a, b in zip(segsA, segsB):
@@ -253,17 +299,30 @@ def test_ballquery_fuse_matches_oracle(st):
     cap = len(P) + 16
     Pp = np.full((cap, 3), 9.0); Pp[:len(P)] = P
     px, py, pz = _t(Pp[:, 0]), _t(Pp[:, 1]), _t(Pp[:, 2])
-    S = len(cases)
+    S = len(segsA)
     cnt_a = _t(np.array([len(a) for a in segsA], np.int32))
     cnt_b = _t(np.array([len(b) for b in segsB], np.int32))
-    tb = _t(np.array(base_b, np.int64))
-    st.ballquery_fuse(px, py, pz, _t(np.array(base_a, np.int64)), cnt_a, tb, cnt_b, 0.1, S, cap,
-                      torch.zeros(2 * S + 2, dtype=torch.int32, device=DEV),
-                      torch.zeros(cap, dtype=torch.uint8, device=DEV))
+    ta, tb = _t(np.array(base_a, np.int64)), _t(np.array(base_b, np.int64))
+    tile_off = alloc(2 * S + 2, torch.int32)
+    flags = alloc(cap, torch.uint8)
+    if radius is None:
+        st.ballquery_fuse(px, py, pz, ta, cnt_a, tb, cnt_b, 0.1, S, cap, tile_off, flags)
+    else:
+        queue = alloc(st.rf_queue_ints(cap), torch.int32)
+        st.radius_filter(px, py, pz, tb, cnt_b, _t(radius), 1, S, cap, tile_off, flags, queue,
+                         phases=st.RF_ALL & ~st.RF_COMPACT)
+        st.ballquery_fuse(px, py, pz, ta, cnt_a, tb, cnt_b, 0.1, S, cap, tile_off, flags, masked=True)
     torch.cuda.synchronize()
     X = torch.stack([px, py, pz], 1).cpu().numpy()
-    ncb = cnt_b.cpu().numpy()
-    nbase = tb.cpu().numpy()
+    return base_a, cnt_b.cpu().numpy(), tb.cpu().numpy(), X
+
+
+FUSE_CASES = [(0, 10), (10, 0), (40, 300), (1, 50), (1500, 2600), (3, 3), (4500, 900), (4096, 5000)]
+MASKED_FUSE_CASES = [(0, 40), (30, 0), (60, 700), (900, 4000), (5, 5), (4200, 3000)]
+MASKED_FUSE_RADIUS = np.array([0.6, 3.0, 0.6, 3.0, 0.6, 3.0])
+
+
+def _ballquery_fuse_verify(segsA, segsB, base_a, ncb, nbase, X):
     for s, (a, b) in enumerate(zip(segsA, segsB)):
         keep = O.ball_query(b, a, 0.1) if len(a) and len(b) else np.ones(len(b), bool)
         assert ncb[s] == keep.sum(), s
@@ -272,46 +331,7 @@ def test_ballquery_fuse_matches_oracle(st):
         assert np.array_equal(X[base_a[s]:base_a[s] + len(exp)], exp), s
 
 
-def test_masked_ballquery_equals_filter_then_fuse(st):
-    """radius filter without its compaction + dfu3d_ballquery_fuse_masked == the two stages one after the
-    other (my_loader.py:587-605), checked against the oracle's filter and fuse."""
-    rng = np.random.default_rng(121)
-    cases = [(0, 40), (30, 0), (60, 700), (900, 4000), (5, 5), (4200, 3000)]
-    segsA, segsB = [], []
-    for na, nb in cases:
-        a = rng.normal(0, 2.0, (na, 3))
-        b = rng.normal(0, 2.0, (nb, 3))
-        if na and nb:
-            h = nb // 2
-            b[:h] = a[rng.integers(0, na, h)] + rng.normal(0, 0.06, (h, 3))
-            far = rng.random(nb) < 0.2                              # isolated pseudo points: the filter drops them
-            b[far] = rng.uniform(-300, 300, (int(far.sum()), 3))
-        segsA.append(a)
-        segsB.append(b)
-    chunks, base_a, base_b, cur = [], [], [], 0
-    for a, b in zip(segsA, segsB):
-        base_a.append(cur); cur += len(a)
-        base_b.append(cur); cur += len(b)
-        chunks += [a, b]
-    P = np.concatenate(chunks)
-    cap = len(P) + 16
-    Pp = np.full((cap, 3), 9.0); Pp[:len(P)] = P
-    px, py, pz = _t(Pp[:, 0]), _t(Pp[:, 1]), _t(Pp[:, 2])
-    S = len(cases)
-    cnt_a = _t(np.array([len(a) for a in segsA], np.int32))
-    cnt_b = _t(np.array([len(b) for b in segsB], np.int32))
-    ta, tb = _t(np.array(base_a, np.int64)), _t(np.array(base_b, np.int64))
-    radius = _t(np.array([0.6, 3.0, 0.6, 3.0, 0.6, 3.0]))
-    tile_off = torch.zeros(2 * S + 2, dtype=torch.int32, device=DEV)
-    flags = torch.zeros(cap, dtype=torch.uint8, device=DEV)
-    queue = torch.zeros(st.rf_queue_ints(cap), dtype=torch.int32, device=DEV)
-    st.radius_filter(px, py, pz, tb, cnt_b, radius, 1, S, cap, tile_off, flags, queue,
-                     phases=st.RF_ALL & ~st.RF_COMPACT)
-    st.ballquery_fuse(px, py, pz, ta, cnt_a, tb, cnt_b, 0.1, S, cap, tile_off, flags, masked=True)
-    torch.cuda.synchronize()
-    X = torch.stack([px, py, pz], 1).cpu().numpy()
-    ncb = cnt_b.cpu().numpy()
-    r = radius.cpu().numpy()
+def _masked_fuse_verify(segsA, segsB, r, base_a, ncb, X):
     for s, (a, b) in enumerate(zip(segsA, segsB)):
         b1 = b[O.radius_outlier(b, 1, r[s])] if len(b) else b
         keep = O.ball_query(b1, a, 0.1) if len(a) and len(b1) else np.ones(len(b1), bool)
@@ -320,26 +340,54 @@ def test_masked_ballquery_equals_filter_then_fuse(st):
         assert np.array_equal(X[base_a[s]:base_a[s] + len(exp)], exp), s
 
 
+def test_ballquery_fuse_matches_oracle(st):
+    segsA, segsB = _fuse_segments(12, FUSE_CASES)
+    base_a, ncb, nbase, X = _ballquery_fuse_run(st, segsA, segsB)
+    _ballquery_fuse_verify(segsA, segsB, base_a, ncb, nbase, X)
+
+
+def test_masked_ballquery_equals_filter_then_fuse(st):
+    """radius filter without its compaction + dfu3d_ballquery_fuse_masked == the two stages one after the
+    other (my_loader.py:587-605), checked against the oracle's filter and fuse."""
+    segsA, segsB = _fuse_segments(121, MASKED_FUSE_CASES, far=True)
+    base_a, ncb, _, X = _ballquery_fuse_run(st, segsA, segsB, radius=MASKED_FUSE_RADIUS)
+    _masked_fuse_verify(segsA, segsB, MASKED_FUSE_RADIUS, base_a, ncb, X)
+
+
 # ------------------------------------------------------------------ a11
-def test_stat_filter_matches_oracle(st):
-    rng = np.random.default_rng(11)
-    segs = [_clustered_points(rng, n, 0.5, 0.1) for n in (0, 1, 2, 31, 400, 1300)]
+STAT_SIZES = (0, 1, 2, 31, 400, 1300)
+
+
+def _stat_filter_run(st, segs, enable, nb_neighbors, std_ratio, alloc=_zeros):
+    """-> (segment bases, counts after, pool after)"""
     P, base, cnt, cap = _pool_from_segments(segs)
     px, py, pz = _t(P[:, 0]), _t(P[:, 1]), _t(P[:, 2])
     S = len(segs)
     seg_cnt = _t(cnt)
-    enable = np.ones(S, np.int32); enable[3] = 0
-    st.stat_filter(px, py, pz, _t(base), seg_cnt, _t(enable), 30, 0.3, S, cap,
-                   torch.zeros(S + 1, dtype=torch.int32, device=DEV),
-                   torch.zeros(cap, dtype=torch.uint8, device=DEV),
-                   torch.zeros(cap, dtype=torch.float64, device=DEV))
+    st.stat_filter(px, py, pz, _t(base), seg_cnt, _t(enable), nb_neighbors, std_ratio, S, cap,
+                   alloc(S + 1, torch.int32),
+                   alloc(cap, torch.uint8),
+                   alloc(cap, torch.float64))
     torch.cuda.synchronize()
     X = torch.stack([px, py, pz], 1).cpu().numpy()
     out = seg_cnt.cpu().numpy()
+    return base, out, X
+
+
+def _stat_filter_verify(segs, enable, nb_neighbors, std_ratio, base, out, X):
     for s, pts in enumerate(segs):
-        keep = O.statistical_outlier(pts, 30, 0.3) if enable[s] else np.arange(len(pts))
+        keep = O.statistical_outlier(pts, nb_neighbors, std_ratio) if enable[s] else np.arange(len(pts))
         assert out[s] == len(keep), (s, out[s], len(keep))
         assert np.array_equal(X[base[s]:base[s] + out[s]], pts[keep]), s
+
+
+def test_stat_filter_matches_oracle(st):
+    rng = np.random.default_rng(11)
+    segs = [_clustered_points(rng, n, 0.5, 0.1) for n in STAT_SIZES]
+    S = len(segs)
+    enable = np.ones(S, np.int32); enable[3] = 0
+    base, out, X = _stat_filter_run(st, segs, enable, 30, 0.3)
+    _stat_filter_verify(segs, enable, 30, 0.3, base, out, X)
 
 
 # ------------------------------------------------------------------ a13
@@ -368,6 +416,31 @@ def _cluster_cases(rng):
     return cases
 
 
+def _range_cluster_run(st, cases, R0, Rd, alloc=None):
+    """alloc=None: labels pre-filled with -7 and the stage's own scratch, as this file's test makes them.
+    -> (segment bases, labels)"""
+    segs = [np.concatenate([c, np.zeros((len(c), 1))], 1) for c in cases]
+    P, base, cnt, cap = _pool_from_segments(segs)
+    px, py = _t(P[:, 0]), _t(P[:, 1])
+    S = len(segs)
+    if alloc is None:
+        label = torch.full((cap,), -7, dtype=torch.int32, device=DEV)
+        st.range_cluster(px, py, _t(base), _t(cnt), S, R0, Rd, label, cap)
+    else:
+        label = alloc(cap, torch.int32)
+        st.range_cluster(px, py, _t(base), _t(cnt), S, R0, Rd, label, cap, sx=alloc(cap, torch.float64),
+                         sy=alloc(cap, torch.float64), si=alloc(3 * cap, torch.int32))
+    torch.cuda.synchronize()
+    lab = label.cpu().numpy()
+    return base, lab
+
+
+def _range_cluster_verify(cases, R0, Rd, base, lab):
+    for s, c in enumerate(cases):
+        exp = O.range_cluster_labels(c[:, 0], c[:, 1], R0, Rd)
+        assert np.array_equal(lab[base[s]:base[s] + len(c)], exp), s
+
+
 @pytest.mark.parametrize("R0,Rd", [(3.0, 0.001), (3.0, 0.0), (3.0, 0.05), (0.6, 0.001)])
 def test_range_cluster_matches_oracle(st, R0, Rd):
     """(3.0, 0.001): the reference's radii, every case.  Rd = 0: one radius for all points (the grid's margin is all that
@@ -378,27 +451,39 @@ def test_range_cluster_matches_oracle(st, R0, Rd):
     cases = _cluster_cases(rng)
     if (R0, Rd) != (3.0, 0.001):
         cases = [c for c in cases if len(c) < 29000]
-    segs = [np.concatenate([c, np.zeros((len(c), 1))], 1) for c in cases]
-    P, base, cnt, cap = _pool_from_segments(segs)
-    px, py = _t(P[:, 0]), _t(P[:, 1])
-    S = len(segs)
-    label = torch.full((cap,), -7, dtype=torch.int32, device=DEV)
-    st.range_cluster(px, py, _t(base), _t(cnt), S, R0, Rd, label, cap)
-    torch.cuda.synchronize()
-    lab = label.cpu().numpy()
-    for s, c in enumerate(cases):
-        exp = O.range_cluster_labels(c[:, 0], c[:, 1], R0, Rd)
-        assert np.array_equal(lab[base[s]:base[s] + len(c)], exp), s
+    base, lab = _range_cluster_run(st, cases, R0, Rd)
+    _range_cluster_verify(cases, R0, Rd, base, lab)
 
 
 # ------------------------------------------------------------------ a14/a15
-def test_lshape_fit_matches_oracle(st):
-    from dfu3d_amd import synth
-    from dfu3d_amd.params import Params
+def _lshape_fit_run(st, segs, M, cals, classes, iscar, boxes, scores, p, n_theta, dtheta, alloc=_zeros):
+    """dfu3d_range_cluster, then dfu3d_lshape_fit over the segments -> (status word, rows (n, ROW_DOUBLES))."""
+    S = len(segs)
+    P, base, cnt, cap = _pool_from_segments(segs)
+    px, py, pz = _t(P[:, 0]), _t(P[:, 1]), _t(P[:, 2])
+    tb, tc = _t(base), _t(cnt)
+    label = alloc(cap, torch.int32)
+    st.range_cluster(px, py, tb, tc, S, p.R0, p.Rd, label, cap)
+    cap_rows = 64
+    rows = alloc(cap_rows * st.ROW_DOUBLES, torch.float64)
+    n_rows = torch.zeros(1, dtype=torch.int32, device=DEV)
+    status = torch.zeros(1, dtype=torch.int32, device=DEV)
+    calib = _t(np.stack([c.record() for c in cals]))
+    st.lshape_fit(px, py, pz, label, tb, tc, S, M, calib, _t(np.array(classes, np.int32)),
+                  _t(np.array(iscar, np.int32)), _t(np.array(boxes, np.float32)),
+                  _t(np.array(scores, np.float32)), n_theta, dtheta,
+                  p.car_aspect_max, alloc(cap, torch.float64),
+                  alloc(cap, torch.float64),
+                  alloc(cap, torch.int32), cap_rows, rows, n_rows,
+                  status, cap)
+    torch.cuda.synchronize()
+    n = int(n_rows.item())
+    return int(status.item()), rows.view(cap_rows, st.ROW_DOUBLES)[:n].cpu().numpy()
+
+
+def _lshape_case():
+    """-> (segments, M, calibrations, classes, is-car flags, 2-D boxes, scores) of test_lshape_fit_matches_oracle"""
     rng = np.random.default_rng(14)
-    p = Params()
-    n_theta, dtheta = p.thetas()
-    assert n_theta == 89
     M = 4
     segs, classes, iscar, boxes = [], [], [], []
     def lshape(cx, cy, L, Wd, yaw, n):
@@ -425,27 +510,19 @@ def test_lshape_fit_matches_oracle(st):
     V = S // M
     cals = [_rand_calib(rng, (30.0, -55.0, 110.0)[v % 3]) for v in range(V)]      # a calibration per view
     scores = [0.1 + 0.8 * ((5 * s + 2) % S) / S for s in range(S)]                # a score per instance
-    P, base, cnt, cap = _pool_from_segments(segs)
-    px, py, pz = _t(P[:, 0]), _t(P[:, 1]), _t(P[:, 2])
-    tb, tc = _t(base), _t(cnt)
-    label = torch.zeros(cap, dtype=torch.int32, device=DEV)
-    st.range_cluster(px, py, tb, tc, S, p.R0, p.Rd, label, cap)
-    cap_rows = 64
-    rows = torch.zeros(cap_rows * st.ROW_DOUBLES, dtype=torch.float64, device=DEV)
-    n_rows = torch.zeros(1, dtype=torch.int32, device=DEV)
-    status = torch.zeros(1, dtype=torch.int32, device=DEV)
-    calib = _t(np.stack([c.record() for c in cals]))
-    st.lshape_fit(px, py, pz, label, tb, tc, S, M, calib, _t(np.array(classes, np.int32)),
-                  _t(np.array(iscar, np.int32)), _t(np.array(boxes, np.float32)),
-                  _t(np.array(scores, np.float32)), n_theta, dtheta,
-                  p.car_aspect_max, torch.zeros(cap, dtype=torch.float64, device=DEV),
-                  torch.zeros(cap, dtype=torch.float64, device=DEV),
-                  torch.zeros(cap, dtype=torch.int32, device=DEV), cap_rows, rows, n_rows,
-                  status, cap)
-    torch.cuda.synchronize()
-    assert int(status.item()) == 0
-    n = int(n_rows.item())
-    R = rows.view(cap_rows, st.ROW_DOUBLES)[:n].cpu().numpy()
+    return segs, M, cals, classes, iscar, boxes, scores
+
+
+def test_lshape_fit_matches_oracle(st):
+    from dfu3d_amd.params import Params
+    p = Params()
+    n_theta, dtheta = p.thetas()
+    assert n_theta == 89
+    segs, M, cals, classes, iscar, boxes, scores = _lshape_case()
+    V = len(segs) // M
+    status, R = _lshape_fit_run(st, segs, M, cals, classes, iscar, boxes, scores, p, n_theta, dtheta)
+    assert status == 0
+    n = len(R)
     exp, _ = F.expected_rows(segs, M, classes, iscar, boxes, scores, [_oracle_calib(c) for c in cals], O.Params())
     assert n == len(exp) and V == 2, (n, len(exp))
     F.assert_rows_match(R, exp, dtheta)         # all 24 columns: class, box, score, members, heading index, extents, root
@@ -498,25 +575,9 @@ def test_lshape_fit_heading_ties_are_decided_like_the_reference(st):
     V = S // M
     cals = [_rand_calib(rng, (30.0, -55.0, 110.0)[v % 3]) for v in range(V)]      # a calibration per view
     scores = [0.1 + 0.8 * ((5 * s + 2) % S) / S for s in range(S)]                # a score per instance
-    P, base, cnt, cap = _pool_from_segments(segs)
-    px, py, pz = _t(P[:, 0]), _t(P[:, 1]), _t(P[:, 2])
-    tb, tc = _t(base), _t(cnt)
-    label = torch.zeros(cap, dtype=torch.int32, device=DEV)
-    st.range_cluster(px, py, tb, tc, S, p.R0, p.Rd, label, cap)
-    cap_rows = 64
-    rows = torch.zeros(cap_rows * st.ROW_DOUBLES, dtype=torch.float64, device=DEV)
-    n_rows = torch.zeros(1, dtype=torch.int32, device=DEV)
-    status = torch.zeros(1, dtype=torch.int32, device=DEV)
-    st.lshape_fit(px, py, pz, label, tb, tc, S, M, _t(np.stack([c.record() for c in cals])), _t(np.array(classes, np.int32)),
-                  _t(np.array(iscar, np.int32)), _t(np.array(boxes, np.float32)),
-                  _t(np.array(scores, np.float32)), n_theta, dtheta,
-                  p.car_aspect_max, torch.zeros(cap, dtype=torch.float64, device=DEV),
-                  torch.zeros(cap, dtype=torch.float64, device=DEV),
-                  torch.zeros(cap, dtype=torch.int32, device=DEV), cap_rows, rows, n_rows, status, cap)
-    torch.cuda.synchronize()
-    assert int(status.item()) == 0
-    n = int(n_rows.item())
-    R = rows.view(cap_rows, st.ROW_DOUBLES)[:n].cpu().numpy()
+    status, R = _lshape_fit_run(st, segs, M, cals, classes, iscar, boxes, scores, p, n_theta, dtheta)
+    assert status == 0
+    n = len(R)
     exp, _ = F.expected_rows(segs, M, classes, iscar, boxes, scores, [_oracle_calib(c) for c in cals], O.Params())
     assert n == len(exp) and n >= 8 and V == 2, (n, len(exp))
     # column 18 of the engine row is the chosen heading: the oracle's (= the reference's) arg-max, exactly -- compared as
@@ -534,25 +595,37 @@ def _lidar_setup(seed, n_frames=2, cams=3, H=225, W=400, M=4):
     return scenes, p
 
 
-def test_fov_plane_label_match_oracle(st):
-    from dfu3d_amd import synth
-    scenes, p = _lidar_setup(20)
-    H, W = p.bounds_hw
-    b = synth.to_view_batch(scenes, p, DEV)
+def _fov_plane_run(st, b, p, cap_n, alloc=_zeros):
+    """dfu3d_fov_filter and dfu3d_plane_ransac over the batch -> (fov_idx, n_fov, plane), on the device."""
     V = b.view_frame.numel()
-    M = b.masks.shape[1]
-    cap_n = max(s.points.shape[0] for s in scenes)
-    i32 = lambda n: torch.zeros(n, dtype=torch.int32, device=DEV)
-    f64 = lambda n: torch.zeros(n, dtype=torch.float64, device=DEV)
+    i32 = lambda n: alloc(n, torch.int32)
+    f64 = lambda n: alloc(n, torch.float64)
     fov_idx, n_fov = i32(V * cap_n), i32(V)
     st.fov_filter(b.points, b.pt_off, b.view_frame, b.calib, V, p.fov_hw, cap_n, fov_idx, n_fov,
                   b.host_pt_off, b.host_view_frame)
     plane = f64(V * 4)
     st.plane_ransac(b.points, b.pt_off, b.view_frame, fov_idx, n_fov, V, cap_n, p.plane_max_hs,
                     p.plane_range, p.ransac_trials, p.ransac_seed, b.view_key, i32(V * cap_n), plane)
+    return fov_idx, n_fov, plane
+
+
+def _project_label_run(st, b, p, cap_n, planes, fov_idx, n_fov, alloc=_zeros):
+    """dfu3d_project_label with the given planes -> (n_ag, K, it_bits, it_x, it_y, it_z), on the device."""
+    H, W = p.bounds_hw
+    V = b.view_frame.numel()
+    M = b.masks.shape[1]
+    i32 = lambda n: alloc(n, torch.int32)
+    f64 = lambda n: alloc(n, torch.float64)
     ag_pt, ib_pix, n_ag, K = i32(V * cap_n), i32(V * cap_n), i32(V), i32(V)
     bits, ix, iy, iz = i32(V * cap_n), f64(V * cap_n), f64(V * cap_n), f64(V * cap_n)
-    # oracle planes go in so that the integer comparison below is apples to apples
+    st.project_label(b.points, b.pt_off, b.view_frame, b.calib, _t(planes.reshape(-1)), fov_idx,
+                     n_fov, b.masks, b.n_inst, V, M, H, W, cap_n, p.plane_offset, p.plane_range,
+                     ag_pt, ib_pix, n_ag, K, bits, ix, iy, iz)
+    torch.cuda.synchronize()
+    return n_ag, K, bits, ix, iy, iz
+
+
+def _oracle_planes(scenes, p):
     op = O.Params(bounds_hw=p.bounds_hw, fov_hw=p.fov_hw)
     planes_o = []
     v = 0
@@ -562,13 +635,11 @@ def test_fov_plane_label_match_oracle(st):
             lid, flag = O.fov_filter(s.points.numpy(), oc, p.fov_hw)
             planes_o.append(O.plane_ransac(lid[:, :3], op, key=v))
             v += 1
-    planes_o = np.array(planes_o)
-    torch.cuda.synchronize()
-    np.testing.assert_allclose(plane.cpu().numpy().reshape(V, 4), planes_o, rtol=1e-9, atol=1e-9)
-    st.project_label(b.points, b.pt_off, b.view_frame, b.calib, _t(planes_o.reshape(-1)), fov_idx,
-                     n_fov, b.masks, b.n_inst, V, M, H, W, cap_n, p.plane_offset, p.plane_range,
-                     ag_pt, ib_pix, n_ag, K, bits, ix, iy, iz)
-    torch.cuda.synchronize()
+    return np.array(planes_o)
+
+
+def _fov_label_verify(scenes, p, cap_n, planes_o, fov_idx, n_fov, n_ag, K, bits, ix, iy, iz):
+    V = n_fov.numel()
     fov_idx_h, n_fov_h = fov_idx.cpu().numpy().reshape(V, cap_n), n_fov.cpu().numpy()
     n_ag_h, K_h = n_ag.cpu().numpy(), K.cpu().numpy()
     bits_h = bits.cpu().numpy().reshape(V, cap_n)
@@ -589,6 +660,21 @@ def test_fov_plane_label_match_oracle(st):
                 got = np.nonzero((bits_h[v, :Ko] >> j) & 1)[0]
                 assert np.array_equal(got, rows[j]), (v, j)
             v += 1
+
+
+def test_fov_plane_label_match_oracle(st):
+    from dfu3d_amd import synth
+    scenes, p = _lidar_setup(20)
+    b = synth.to_view_batch(scenes, p, DEV)
+    V = b.view_frame.numel()
+    cap_n = max(s.points.shape[0] for s in scenes)
+    fov_idx, n_fov, plane = _fov_plane_run(st, b, p, cap_n)
+    # oracle planes go in so that the integer comparison below is apples to apples
+    planes_o = _oracle_planes(scenes, p)
+    torch.cuda.synchronize()
+    np.testing.assert_allclose(plane.cpu().numpy().reshape(V, 4), planes_o, rtol=1e-9, atol=1e-9)
+    n_ag, K, bits, ix, iy, iz = _project_label_run(st, b, p, cap_n, planes_o, fov_idx, n_fov)
+    _fov_label_verify(scenes, p, cap_n, planes_o, fov_idx, n_fov, n_ag, K, bits, ix, iy, iz)
 
 
 PLANE_SIZES = [3, 4, 5, 63, 64, 65, 511, 512, 513, 1025, 3073]
@@ -636,19 +722,21 @@ def test_plane_medians_with_tied_heights_match_oracle(tied_planes, n):
 
 
 # ------------------------------------------------------------------ a7/a8/a9
-def _bp_run(st, depth, cal, masks, max_points=100, max_voxels=1000000, key_axis=1, cap_vox=1 << 16, calls=None):
-    """calls: the phase bits of each backproject_bin call of a pass (default: one call with every phase)."""
+def _bp_run(st, depth, cal, masks, max_points=100, max_voxels=1000000, key_axis=1, cap_vox=1 << 16, calls=None,
+            alloc=_zeros):
+    """calls: the phase bits of each backproject_bin call of a pass (default: one call with every phase).
+    alloc: scratch and outputs; n_vox and the status word are the caller's to zero (include/dfu3d.h)."""
     calls = calls or (st.BP_ALL,)
     V, H, W = depth.shape
     geom, E = st.make_geom(max_points_per_voxel=max_points, max_voxels=max_voxels)
     table = torch.empty(V * E * st.TABLE_ENTRY_BYTES, dtype=torch.uint8, device=DEV)
     st.bin_table_init(table, V * E)
     pw, bw = st.backproject_scratch_words(V, H, W, cap_vox, max_points, geom)
-    i32 = lambda n: torch.zeros(n, dtype=torch.int32, device=DEV)
-    f64 = lambda n: torch.zeros(n, dtype=torch.float64, device=DEV)
-    n_vox, vox_pix, bits = i32(V), i32(V * cap_vox), i32(V * cap_vox)
+    i32 = lambda n: alloc(n, torch.int32)
+    f64 = lambda n: alloc(n, torch.float64)
+    n_vox, vox_pix, bits = _zeros(V, torch.int32), i32(V * cap_vox), i32(V * cap_vox)
     x, y, z = f64(V * cap_vox), f64(V * cap_vox), f64(V * cap_vox)
-    status = i32(1)
+    status = _zeros(1, torch.int32)
     M = masks.shape[1]
     calib = _t(np.stack([c.record() for c in cal]))
     n_inst = _t(np.full(V, M, np.int32))
