@@ -247,7 +247,7 @@ inline FastGeom make_fast_geom(const dfu3d_bin_geom &g) {
   // most (1 + |q0|) / w + 1.  A geometry with bins so narrow that this eats the slop gets no tier 1 at all.
   const double slop_t = 1.8e-7 * ((1.0 + __builtin_fabs(f.tq0d)) / f.twd + 1.0), slop_p = 1.8e-7 * ((1.0 + __builtin_fabs(f.pq0d)) / f.pwd + 1.0);
   if (!(__builtin_fmax(slop_t, slop_p) <= TAB_SLOP_W)) f.dmax = 0.0f;
-  if (g.t_n >= (1 << 16) || g.p_n >= (1 << 16)) f.dmax = 0.0f;          // k_bp_bin packs the window coordinates into 16 + 16 bits (classify_fast forms the bin index with a 24-bit multiply)
+  if (g.t_n >= (1 << 16) || g.p_n >= (1 << 16)) f.dmax = 0.0f;          // k_bp_bin packs the window coordinates into 16 + 16 bits (and the bin index it_k * p_n + ip_k stays below 2^32)
   // tier 1.5: one fp64 edge per bin boundary of the window behind the float32 tables, if the scratch holds them
   f.mid_ok = (f.dmax > 0.0f) && ((int64_t)f.tJ + f.pJ + 4 + (int64_t)g.t_n + g.p_n + 2 <= 2 * (int64_t)(TAB_T_MAX + TAB_P_MAX));
   f.pad1 = 0;
@@ -334,17 +334,10 @@ __global__ void k_bp_tables(dfu3d_bin_geom g, FastGeom fg, float2 *__restrict__ 
   tables_entry(i, g, fg, tab);
 }
 
-// bin of q from the axis' table; false = undecided (no branches: garbage in -- NaN, an index off the table -- meets
-// a NaN entry and fails the comparison).  The index is clamped as an unsigned number: a negative one lands on the upper
-// sentinel like one that is too large.
-__device__ __forceinline__ bool tab_bin(const float2 *__restrict__ tab, float inv_w, float c1, int J, float q,
-                                        float delta, uint32_t &k) {
-  const uint32_t j = min((uint32_t)(int)__fmaf_rn(q, inv_w, c1), (uint32_t)(J + 1));
-  const float2 e = *(const float2 *)((const char *)tab + (j << 3));      // 32-bit offset from a uniform base
-  const float t = q - e.x;
-  k = (uint32_t)(__float_as_int(e.y) + (__float_as_int(t) >> 31));       // below the edge: the bin under it
-  return fabsf(t) > delta;
-}
+// The cell of q in the axis' table (classify_fast reads the bin of q from it without a branch: garbage in -- NaN, an
+// index off the table -- meets a NaN entry and fails the comparison).  The index is clamped as an unsigned number: a
+// negative one lands on the upper sentinel like one that is too large.
+__device__ __forceinline__ uint32_t tab_cell(float cell, int J) { return min((uint32_t)(int)cell, (uint32_t)(J + 1)); }
 
 // ---- float32 back-projection estimate ------------------------------------------------------------
 // calibration_kitti.py:134-144 + 89-102 collapse, per LiDAR coordinate j, to
@@ -476,61 +469,135 @@ __device__ __forceinline__ void backproject_f32(const FastCal &fc, int col, int 
 // dfu3d_selftest_classify() runs this function against pixel_bin() on random pixels of the real geometry and
 // calibration: the GPU tests require zero disagreements among the decided ones.
 // The exact fp64 coordinate that serves as the voxel key is computed only for pixels that are kept (want_key).
-// N pixels of one image row, straight-line code (the decisions of the N pixels are independent; written this way the
-// compiler interleaves their transcendental and table latencies and pairs their float32 arithmetic): res[k] = NOBIN
-// (certainly not binned), AMBIG (tier 2 decides) or the table index, with it / ip the window coordinates of the bin.
+// N pixels of one image row: res[k] = NOBIN (certainly not binned), AMBIG (tier 2 decides) or the table index, with
+// it / ip the window coordinates of the bin.  The decisions of the N pixels are independent, and until round 9 the code
+// was one straight-line statement of a single pixel, unrolled N times, in the belief that the compiler would interleave
+// the pixels' table latencies and pair their arithmetic.  It did neither well (gfx950 assembly, profiles/r09_isa_mix.txt):
+// every pixel waited for its own two gathers inside an exec-mask region of its own -- eight dependent round trips per
+// thread -- and the 74 operations the compiler paired itself cost 108 register moves.  Now the pairing is written out:
+// pixels k, k + 1 live in ONE register pair from the depth load on, and multiplies, adds and FMAs of two vectors are
+// packed (v_pk_*_f32: one issue slot for both); compares, selects, v_rsq / v_rcp, the table gathers and everything with a
+// uniform operand work on the elements.  Each element sees the IEEE operations of backproject_f32 and of the budget
+// above on the same operands in the same order -- (x x + y y) + z z, (err ir) sqrt(3), (1.1 turn) rsq(s2), ... -- so a
+// decided pixel gets the bin it got before, bit for bit (pixel_bin_fast, N = 1, runs the same code with a dead partner).
+// The row piece is done in three steps: everything up to the table cells of all N pixels, the 2 N gathers back to back,
+// the decisions as selects.  Measured with tools/ab_builds.py: bp_bin 2.207 -> 2.053 ms per 384-view pass
+// (profiles/r09_ab_bench.log); statically 885 -> 801 vector instructions between the first two barriers.
+typedef float f32x2 __attribute__((ext_vector_type(2)));
+__device__ __forceinline__ f32x2 fma2(f32x2 a, f32x2 b, f32x2 c) { return __builtin_elementwise_fma(a, b, c); }
+// one operand the same for both elements (a kernel argument, a per-view constant, a literal): NOT packed either -- a packed
+// instruction takes no literal and reads a uniform operand as a register PAIR, which the compiler fills with two copies
+// of it: written packed, these operations took 46 scalar registers for their 23 constants and the kernel spilled 23
+// (el(): the element as an opaque value, no instruction -- without it the compiler's own pairing puts the two halves
+// back together)
+__device__ __forceinline__ float el(float x) { asm("" : "+v"(x)); return x; }
+__device__ __forceinline__ f32x2 fma_s(f32x2 a, float s, f32x2 c) { return f32x2{el(__fmaf_rn(a.x, s, c.x)), el(__fmaf_rn(a.y, s, c.y))}; }
+__device__ __forceinline__ f32x2 fma_ss(f32x2 a, float s, float c) { return f32x2{el(__fmaf_rn(a.x, s, c)), el(__fmaf_rn(a.y, s, c))}; }
+__device__ __forceinline__ f32x2 mul_s(float s, f32x2 a) { return f32x2{el(s * a.x), el(s * a.y)}; }
+__device__ __forceinline__ f32x2 add_s(float s, f32x2 a) { return f32x2{el(s + a.x), el(s + a.y)}; }
+__device__ __forceinline__ f32x2 sub_s(float s, f32x2 a) { return f32x2{el(s - a.x), el(s - a.y)}; }
+__device__ __forceinline__ f32x2 rsq2(f32x2 a) { return f32x2{__builtin_amdgcn_rsqf(a.x), __builtin_amdgcn_rsqf(a.y)}; }
+// |a| + |b| and a + |b| per element, NOT packed: the absolute value is an operand modifier of v_add_f32 and a v_and_b32
+// of its own in front of v_pk_add_f32
+__device__ __forceinline__ f32x2 add_abs2(f32x2 a, f32x2 b) { return f32x2{a.x + fabsf(b.x), a.y + fabsf(b.y)}; }
+__device__ __forceinline__ f32x2 abs_add_abs2(f32x2 a, f32x2 b) { return f32x2{fabsf(a.x) + fabsf(b.x), fabsf(a.y) + fabsf(b.y)}; }
+
 template <int N>
 __device__ __forceinline__ void classify_fast(const FastCal &fc, const HotGeom &fg,
                                               const float2 *__restrict__ tab, int row, const int (&col)[N],
                                               const float (&d)[N], uint32_t (&res)[N], int (&it)[N], int (&ip)[N]) {
-  float xf[N], yf[N], zf[N], err[N];
-  bool dead[N];
+  constexpr int NP = (N + 1) / 2;                    // pairs (k, k + 1); an odd N pads its last pair with a dead pixel (depth 0)
+  f32x2 d2[NP], xf[NP], yf[NP], zf[NP], err[NP];
+  bool dead[2 * NP];
   bool any_live = false;
+  // the row's part of W_j, the same for every pixel of the row
+  const float v = (float)row;
+  const float bv0 = __fmaf_rn(fc.b[0], v, fc.c[0]), bv1 = __fmaf_rn(fc.b[1], v, fc.c[1]), bv2 = __fmaf_rn(fc.b[2], v, fc.c[2]);
 #pragma unroll
-  for (int k = 0; k < N; k++) {
-    backproject_f32(fc, col[k], row, d[k], xf[k], yf[k], zf[k], err[k]);
-    const bool dok = depth_live(d[k], fg.depth_min);
-    dead[k] = !dok || (zf[k] > fg.z_max + err[k]);                       // certainly z >= z_max (my_loader.py:540)
-    any_live = any_live || !dead[k];
-    res[k] = NOBIN; it[k] = 0; ip[k] = 0;
+  for (int p = 0; p < NP; p++) {
+    const int k1 = 2 * p + 1 < N ? 2 * p + 1 : N - 1;
+    d2[p] = f32x2{d[2 * p], 2 * p + 1 < N ? d[k1] : 0.0f};
+    const f32x2 u = {(float)col[2 * p], (float)col[k1]};
+    const f32x2 w0 = fma_s(u, fc.a[0], f32x2(bv0)), w1 = fma_s(u, fc.a[1], f32x2(bv1)), w2 = fma_s(u, fc.a[2], f32x2(bv2));
+    xf[p] = fma2(d2[p], w0, f32x2(fc.e[0]));
+    yf[p] = fma2(d2[p], w1, f32x2(fc.e[1]));
+    zf[p] = fma2(d2[p], w2, f32x2(fc.e[2]));
+    // backproject_f32's bound with d for |d|: the same number for a live pixel (d > 0), and a dead one is NOBIN whatever
+    // its bound comes to (NaN included)
+    err[p] = mul_s(2.3841858e-07f, add_abs2(add_abs2(add_abs2(fma_ss(d2[p], fc.wsum, fc.esum), xf[p]), yf[p]), zf[p]));
+    const f32x2 zhi = add_s(fg.z_max, err[p]);
+    dead[2 * p] = !depth_live(d2[p].x, fg.depth_min) || (zf[p].x > zhi.x);    // certainly z >= z_max (my_loader.py:540)
+    dead[2 * p + 1] = !depth_live(d2[p].y, fg.depth_min) || (zf[p].y > zhi.y);
+    any_live = any_live || !dead[2 * p] || !dead[2 * p + 1];
   }
-  if (!any_live) return;
 #pragma unroll
-  for (int k = 0; k < N; k++) {
-    // `ok` collects the conditions of a decision with & (no short circuits: the masks are combined on the scalar
-    // unit); a NaN anywhere makes one of them false
-    bool ok = zf[k] < fg.z_max - err[k];
-    const float r2 = xf[k] * xf[k] + yf[k] * yf[k] + zf[k] * zf[k];
-    const float ir = __builtin_amdgcn_rsqf(r2);
-    const float rf = r2 * ir;                                            // (NaN for r2 = 0 or inf)
+  for (int k = 0; k < N; k++) { res[k] = NOBIN; it[k] = 0; ip[k] = 0; }
+  if (!any_live) return;
+  // Everything up to the table cells of all N pixels first, then the 2 N gathers back to back, then the decisions: the
+  // gathers of a row piece wait once, together.  `pre` collects the conditions known before the tables are read, with &
+  // (no short circuits); a NaN anywhere makes one of them false.
+  f32x2 qt[NP], qp[NP], dq[NP], dp[NP];
+  uint32_t jt[2 * NP], jp[2 * NP];
+#pragma unroll
+  for (int p = 0; p < NP; p++) {
+    const f32x2 zlo = sub_s(fg.z_max, err[p]);
+    const f32x2 r2 = xf[p] * xf[p] + yf[p] * yf[p] + zf[p] * zf[p];
+    const f32x2 ir = rsq2(r2);
+    const f32x2 rf = r2 * ir;                                              // (NaN for r2 = 0 or inf)
     // r bin: certain only well inside [rmin_r, rmin_r + vsize_r) and for the 1-cell grid; r_lo >= 1e-3 and
     // r_hi <= 1e15 (make_fast_geom), so `rin` also says that r is an ordinary number
-    const float er = 2.5f * err[k];                                      // |rf - r| <= sqrt(3) err + rounding (3 ulp of r <= 0.75 err)
-    const bool rin = (rf - er > fg.r_lo) & (rf + er < fg.r_hi);
-    ok = ok & rin;
-    const float cz = zf[k] * ir;
-    const float s2 = __fmaf_rn(-cz, cz, 1.0f);
-    ok = ok & (s2 > 1e-4f);                                              // near the poles
-    const float turn = err[k] * ir * 1.7320510f;                         // direction error: |(dx,dy,dz)| <= sqrt(3) err
-    const float dq = 1.5e-6f + 1.05f * turn;
-    const float qt = -cz;
-    const bool th_out = rin & (qt < fg.q_tmin - dq);                     // certainly theta <= theta_min (my_loader.py:175)
-    ok = ok & (qt > fg.q_tmin + dq);
-    uint32_t kt, kp;
-    ok = ok & tab_bin(tab, fg.tinv, fg.tc1, fg.tJ, qt, dq, kt);
-    ok = ok & (fabsf(xf[k]) > __fmaf_rn(8.0f, err[k], 1e-20f));          // the sign of x decides the branch of atan(y/x)
-    const float qa = yf[k] * __builtin_amdgcn_rcpf(fabsf(xf[k]) + fabsf(yf[k]));
-    const float qp = xf[k] < 0.0f ? -qa : qa;
-    const float dp = 1.5e-6f + 1.1f * turn * __builtin_amdgcn_rsqf(s2);  // (s2 > 1e-4 or not ok); dp >= dq
-    ok = ok & tab_bin(tab + fg.tJ + 2, fg.pinv, fg.pc1, fg.pJ, qp, dp, kp);
-    ok = ok & (dp < fg.dmax);
-    const uint32_t itk = kt - (uint32_t)fg.t_lo, ipk = kp - (uint32_t)fg.p_lo;      // (wraps for a bin below the window)
-    ok = ok & (itk < (uint32_t)fg.t_n) & (ipk < (uint32_t)fg.p_n);
-    it[k] = (int)itk;                                                    // (meaningful only for a decided, binned pixel)
-    ip[k] = (int)ipk;
-    // (a 24-bit multiply: v_mul_lo_u32 / v_mad_u64_u32 issue at a quarter of the rate; make_fast_geom switches tier 1 off
-    // for a window of 2^24 or more bins along an axis)
-    res[k] = (dead[k] | th_out) ? NOBIN : (ok ? __umul24(itk, (uint32_t)fg.p_n) + ipk : AMBIG);
+    const f32x2 er = mul_s(2.5f, err[p]);                                        // |rf - r| <= sqrt(3) err + rounding (3 ulp of r <= 0.75 err)
+    const f32x2 rlo = rf - er, rhi = rf + er;
+    const f32x2 cz = zf[p] * ir;
+    const f32x2 s2 = fma2(-cz, cz, f32x2(1.0f));
+    const f32x2 turn = mul_s(1.7320510f, err[p] * ir);                           // direction error: |(dx,dy,dz)| <= sqrt(3) err
+    dq[p] = add_s(1.5e-6f, mul_s(1.05f, turn));
+    qt[p] = -cz;
+    const f32x2 tlo = sub_s(fg.q_tmin, dq[p]), thi = add_s(fg.q_tmin, dq[p]);
+    const f32x2 xthr = fma_ss(err[p], 8.0f, 1e-20f);           // the sign of x decides the branch of atan(y/x)
+    const f32x2 den = abs_add_abs2(xf[p], yf[p]);
+    const f32x2 qa = yf[p] * f32x2{__builtin_amdgcn_rcpf(den.x), __builtin_amdgcn_rcpf(den.y)};
+    qp[p] = f32x2{xf[p].x < 0.0f ? -qa.x : qa.x, xf[p].y < 0.0f ? -qa.y : qa.y};
+    dp[p] = add_s(1.5e-6f, mul_s(1.1f, turn) * rsq2(s2));                              // (s2 > 1e-4 or not ok); dp >= dq
+    const f32x2 ct = fma_ss(qt[p], fg.tinv, fg.tc1), cp = fma_ss(qp[p], fg.pinv, fg.pc1);
+#pragma unroll
+    for (int e = 0; e < 2; e++) {
+      const bool rin = (rlo[e] > fg.r_lo) & (rhi[e] < fg.r_hi);
+      const bool th_out = rin & (qt[p][e] < tlo[e]);                       // certainly theta <= theta_min (my_loader.py:175)
+      const bool live = !(dead[2 * p + e] | th_out);
+      const bool pre = live & (zf[p][e] < zlo[e]) & rin & (s2[e] > 1e-4f) /* near the poles */ & (qt[p][e] > thi[e]) &
+                       (fabsf(xf[p][e]) > xthr[e]) & (dp[p][e] < fg.dmax);
+      // what the pixel is without a decision, and a margin no distance exceeds where a condition has failed already: the
+      // masks end here and do not sit in scalar registers across the gathers
+      if (2 * p + e < N) res[2 * p + e] = live ? AMBIG : NOBIN;
+      dq[p][e] = pre ? dq[p][e] : __int_as_float(0x7FC00000);
+      jt[2 * p + e] = tab_cell(ct[e], fg.tJ);
+      jp[2 * p + e] = tab_cell(cp[e], fg.pJ);
+    }
+  }
+  float2 et[2 * NP], ep[2 * NP];
+#pragma unroll
+  for (int k = 0; k < 2 * NP; k++) {
+    et[k] = *(const float2 *)((const char *)tab + (jt[k] << 3));          // 32-bit offsets from a uniform base
+    ep[k] = *(const float2 *)((const char *)(tab + fg.tJ + 2) + (jp[k] << 3));
+  }
+#pragma unroll
+  for (int p = 0; p < NP; p++) {
+    const f32x2 tt = qt[p] - f32x2{et[2 * p].x, et[2 * p + 1].x}, tq = qp[p] - f32x2{ep[2 * p].x, ep[2 * p + 1].x};
+#pragma unroll
+    for (int e = 0; e < 2; e++) {
+      const int k = 2 * p + e;
+      if (k >= N) continue;
+      // below the edge: the bin under it.  A NaN entry (no decision in this cell, q off the table) fails the comparison.
+      const uint32_t kt = (uint32_t)(__float_as_int(et[k].y) + (__float_as_int(tt[e]) >> 31));
+      const uint32_t kp = (uint32_t)(__float_as_int(ep[k].y) + (__float_as_int(tq[e]) >> 31));
+      const uint32_t itk = kt - (uint32_t)fg.t_lo, ipk = kp - (uint32_t)fg.p_lo;    // (wraps for a bin below the window)
+      const bool ok = (fabsf(tt[e]) > dq[p][e]) & (fabsf(tq[e]) > dp[p][e]) & (itk < (uint32_t)fg.t_n) & (ipk < (uint32_t)fg.p_n);
+      it[k] = (int)itk;                                                    // (meaningful only for a decided, binned pixel)
+      ip[k] = (int)ipk;
+      // (make_fast_geom switches tier 1 off for a window of 2^16 or more bins along an axis, so the product fits 32 bits)
+      res[k] = ok ? __umul24(itk, (uint32_t)fg.p_n) + ipk : res[k];
+    }
   }
 }
 
@@ -788,7 +855,7 @@ __global__ __launch_bounds__(PB, P1_OCC) void k_bp_bin(
   const KeyCal kcal = key_cal(c);
   const Recip rc = recip_of(fc);
   const KeyCol kcol = load_key_col(calib + v, key_axis);
-  DBG_T(2);                                        // origin reduction + barrier (= waiting for the slowest wave's classification)
+  DBG_T(2);                                       // origin reduction + barrier (= waiting for the slowest wave's classification)
   // every kept pixel goes to the LDS window on its own.  (Round 2 merged the runs of equal bins among a thread's four
   // consecutive pixels first: fewer LDS atomics, but the bookkeeping of the runs took more vector instructions than the
   // atomics it saved -- the kernel is bound by vector issue, not by the LDS.)
@@ -810,7 +877,11 @@ __global__ __launch_bounds__(PB, P1_OCC) void k_bp_bin(
       const unsigned long long cm = combo_word(ok, base + k, pix_bits);
       const uint32_t lt = it_k - (uint32_t)t0, lp = ip_k - (uint32_t)p0;
       if ((lt < (uint32_t)WIN_T) & (lp < (uint32_t)WIN_P)) {      // aggregate in the LDS window
-        const uint32_t w = __umul24(lt, (uint32_t)WIN_P) + lp;     // (24-bit multiplies issue at four times the rate of v_mul_lo_u32)
+        // (NOT a 24-bit multiply in the code object: the compiler knows lt < 16 here and folds __umul24 and the addition
+        // into one v_mad_u64_u32, a quarter-rate instruction.  Two shift-adds in its place, together with the range test
+        // of the key's two divisions decided once per view: 2.213 ms against 2.207 without, tools/ab_builds.py,
+        // profiles/r09_ab_bench.log -- no gain, not kept)
+        const uint32_t w = __umul24(lt, (uint32_t)WIN_P) + lp;
         atomicAdd(&s_cnt[w], 1u);
         atomicMin(&s_first[w], loc0 + k);
         atomicMin(&s_kmin[w], ok);
@@ -850,7 +921,7 @@ __global__ __launch_bounds__(PB, P1_OCC) void k_bp_bin(
       const uint32_t loc = (uint32_t)((prow - ty * (RPT * TILE_H)) * TILE_W + (pcol - tx * TILE_W));
       const uint32_t lt = mo.it - (uint32_t)t0, lp = mo.ip - (uint32_t)p0;
       if ((lt < (uint32_t)WIN_T) & (lp < (uint32_t)WIN_P)) {
-        const uint32_t w = __umul24(lt, (uint32_t)WIN_P) + lp;     // (24-bit multiplies issue at four times the rate of v_mul_lo_u32)
+        const uint32_t w = __umul24(lt, (uint32_t)WIN_P) + lp;
         atomicAdd(&s_cnt[w], 1u);
         atomicMin(&s_first[w], loc);
         atomicMin(&s_kmin[w], ok);
