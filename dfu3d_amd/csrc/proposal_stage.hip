@@ -6,16 +6,11 @@
 // argsort of the sorted scores, a gather of the box rows, the whole upper triangle of the pre_max x pre_max decision
 // matrix (k_suppress_mask), one wave walking all of its rows (k_nms_reduce), a read of the count, four index assignments.
 //
-//   k_pr_order   one workgroup of 1024 threads per sample: a stable least-significant-digit radix sort, four passes of
-//                eight bits, of (key, point index) under THE ORDER RULE of dfu3d_prop.h (the key here is the rule's key
-//                inverted, so ascending = best first).  Every wave owns a contiguous run of the array; a pass counts the
-//                digits per wave (lanes of equal digit found by eight ballots, the first of them adds their number: no
-//                atomics), scans the 256 x 16 counts digit-major with block_scan_range -- the start of every (digit,
-//                wave) --, and after a barrier (a wave's starts were stored by threads of all waves) every wave scatters
-//                its run in order, moving on its own column of starts without a further barrier.  Pass 0 reads the
-//                scores, the passes between alternate between two buffers in the caller's scratch (128 KiB of keys and
-//                indices for 16 384 points would fit the LDS only once, not twice), pass 3 writes the first K indices.
-//                Equal keys never change places: ascending point index among them.
+//   k_pr_order   one workgroup of 1024 threads per sample: the stable radix sort of block_sort.hpp, of (key, point index)
+//                under THE ORDER RULE of dfu3d_prop.h (the key here is the rule's key inverted, so ascending = best
+//                first).  Pass 0 reads the scores, the passes between alternate between two buffers in the caller's
+//                scratch, pass 3 writes the first K indices.  Equal keys never change places: ascending point index
+//                among them.
 //   k_pr_nms     one workgroup of IB = 256 threads per sample.  A row is suppressed only by a KEPT earlier row and at most
 //                post_max rows are kept, so the kept boxes live in LDS as Rects (make_rect's sincosf once per box, not
 //                once per pair) and the candidates are taken 64 at a time, read through `order`:
@@ -32,6 +27,7 @@
 //                Every pair is decided by nms_suppresses(A, B) with the EARLIER row as A, as in k_suppress_mask and
 //                k_pp_mask: the same bits (a pair the circle test removes has overlap 0 there as here).
 #include "common.hpp"
+#include "block_sort.hpp"
 #include "rect_overlap.hpp"
 #include "dfu3d_prop.h"
 
@@ -76,80 +72,15 @@ __device__ __forceinline__ uint32_t pr_sort_key(float s) {
   return ~key;
 }
 
-// The lanes among `active` whose 8-bit digit equals this lane's (unspecified in a lane that is not active).
-// PRECONDITION: wave-uniform control flow (ballots).
-__device__ __forceinline__ unsigned long long wave_match8(bool active, int digit) {
-  unsigned long long m = __ballot(active);
-#pragma unroll
-  for (int b = 0; b < 8; b++) {
-    const bool bit = (digit >> b) & 1;
-    const unsigned long long v = __ballot(bit);
-    m &= bit ? v : ~v;
-  }
-  return m;
-}
-
-// One pass of the sort over the digit at `shift`.  first: the keys come from the scores and the index is the position;
-// last: only the first K indices are written, to `order`.  cnt: 256 * OW ints of LDS, s_w: OW ints.
-// PRECONDITION: all threads of the workgroup, uniform control flow.
-__device__ __forceinline__ void pr_pass(bool first, bool last, const float *__restrict__ sc, const uint32_t *src_key,
-                                        const int *src_idx, uint32_t *dst_key, int *dst_idx, int *order, int N, int K,
-                                        int shift, int i0, int i1, volatile int *cnt, int *s_w) {
-  const int t = threadIdx.x, w = t >> 6, lane = t & 63;
-  for (int i = t; i < 256 * OW; i += OT) cnt[i] = 0;
-  __syncthreads();
-  for (int base = i0; base < i1; base += 64) {              // uniform per wave
-    const int i = base + lane;
-    const bool act = i < i1;
-    const uint32_t key = act ? (first ? pr_sort_key(sc[i]) : src_key[i]) : 0u;
-    const int d = (int)((key >> shift) & 255u);
-    const unsigned long long m = wave_match8(act, d);
-    if (act && lane == __ffsll((long long)m) - 1) cnt[d * OW + w] += __popcll(m);   // one lane per digit: no atomics
-  }
-  __syncthreads();
-  // digit-major: the start of (digit, wave) = every smaller digit, and the same digit in the waves (= runs) before
-  block_scan_range<OT, 4, int, int>(256 * OW, [&](int i) { return cnt[i]; }, [&](int i, int v) { cnt[i] = v; }, s_w);
-  __syncthreads();                                          // cnt[] is read below by other threads than its writers
-  for (int base = i0; base < i1; base += 64) {
-    const int i = base + lane;
-    const bool act = i < i1;
-    const uint32_t key = act ? (first ? pr_sort_key(sc[i]) : src_key[i]) : 0u;
-    const int idx = act ? (first ? i : src_idx[i]) : 0;
-    const int d = (int)((key >> shift) & 255u);
-    const unsigned long long m = wave_match8(act, d);
-    if (act) {
-      // the wave's lanes read the start in one instruction, then the last lane of every digit moves it on: a wave's
-      // LDS operations are carried out in program order
-      const int start = cnt[d * OW + w];
-      const int pos = start + __popcll(m & ((1ull << lane) - 1ull));
-      if (last) {
-        if (pos < K) order[pos] = idx;
-      } else if ((unsigned)pos < (unsigned)N) {
-        dst_key[pos] = key;
-        dst_idx[pos] = idx;
-      }
-      if (lane == 63 - __clzll((long long)m)) cnt[d * OW + w] = start + __popcll(m);
-    }
-  }
-  __syncthreads();                                          // the scattered rows are the next pass's input
-}
-
 __global__ __launch_bounds__(OT) void k_pr_order(const float *__restrict__ scores, int N, int K, uint32_t *key0,
                                                  int *idx0, uint32_t *key1, int *idx1, int *order) {
   __shared__ int s_cnt[256 * OW];
   __shared__ int s_w[OW];
-  const int b = blockIdx.x, w = threadIdx.x >> 6;
+  const int b = blockIdx.x;
   const size_t o = (size_t)b * N;
   const float *sc = scores + o;
-  uint32_t *ka = key0 + o, *kb = key1 + o;
-  int *ia = idx0 + o, *ib = idx1 + o;
-  const int run = (N + OT - 1) / OT * 64;                   // rows of a wave: a multiple of 64
-  const int i0 = min(w * run, N), i1 = min(i0 + run, N);
-  for (int pass = 0; pass < 4; pass++) {                    // ka -> kb -> ka -> order; pass 0 reads the scores
-    pr_pass(pass == 0, pass == 3, sc, kb, ib, ka, ia, order + (size_t)b * K, N, K, 8 * pass, i0, i1, s_cnt, s_w);
-    uint32_t *tk = ka; ka = kb; kb = tk;
-    int *ti = ia; ia = ib; ib = ti;
-  }
+  block_radix_sort<OT>(N, K, [&](int i) { return pr_sort_key(sc[i]); }, key0 + o, idx0 + o, key1 + o, idx1 + o,
+                       order + (size_t)b * K, s_cnt, s_w);
 }
 
 // The pairs that need the polygon clip, queued in LDS so that the clips run on full waves.  With a pair per lane and the

@@ -20,6 +20,7 @@ sampler's batch draw.
 import numpy as np
 import torch
 
+from .. import point_sample_ops
 from .. import stages as st
 from .._lib import Dfu3dError
 from .database_sampler import DataBaseSampler
@@ -289,7 +290,11 @@ def prepare_batch(data_dicts, augmentor, processor, class_names, training=True, 
     (augmentor.draw_world_params), then one launch chain.  augmentor None: no augmentation.
     Default: ONE host read (n_kept, the B box counts and the status words together) to cut points[:n_kept] and
     gt_boxes[:, :max(gt_cnt)].  as_padded=True: no host read at all; `points` keeps every input row (rows at or beyond
-    `n_kept` carry batch index -1), `gt_boxes` is (B, box_cap, .), and `n_kept`, `point_cnt`, `status` are device tensors."""
+    `n_kept` carry batch index -1), `gt_boxes` is (B, box_cap, .), and `n_kept`, `point_cnt`, `status` are device tensors.
+    A processor with a `sample_points` entry (processor.sample_count()): what the range mask kept of every scene goes
+    through point_sample_ops.sample_points, so `points` is (B * K, 1 + processor.num_point_features) in both forms and
+    `point_cnt` is K for every scene; a scene the mask left without points raises in the default form (the same one
+    read) and sets DFU3D_SMP_EMPTY_SCENE in the last word of `status` in the padded form."""
     B = len(data_dicts)
     if B == 0:
         raise Dfu3dError("prepare_batch: no scenes")
@@ -308,14 +313,27 @@ def prepare_batch(data_dicts, augmentor, processor, class_names, training=True, 
         u['points'], u['point_off'], u['boxes'], u['box_off'], u['box_cnt'], u['box_cls'],
         _h2d(st.aug_params(recs), device), processor.range_tensor(), mode, max(u['box_cap'], 1), status)
     batch = {'batch_size': B, 'gt_cnt': gt_cnt}
+    words = [status] + u['status']
+    k = processor.sample_count()
+    if k is not None:                                      # what the mask kept of every scene -> k rows of it
+        if processor.num_point_features > out.shape[1] - 1:
+            raise Dfu3dError("prepare_batch: the processor's %d point features, the scenes have %d columns"
+                             % (processor.num_point_features, out.shape[1] - 1))
+        out, sampled = point_sample_ops.sample_points(out, point_cnt, k, out_cols=processor.num_point_features)
+        n_kept = torch.full((1,), B * k, dtype=torch.int32, device=device)
+        point_cnt = torch.full((B,), k, dtype=torch.int32, device=device)
+        words.append(sampled)
     if as_padded:
-        batch.update(points=out, gt_boxes=gt, n_kept=n_kept, point_cnt=point_cnt, status=[status] + u['status'])
+        batch.update(points=out, gt_boxes=gt, n_kept=n_kept, point_cnt=point_cnt, status=words)
         return batch
-    host = torch.cat([n_kept, gt_cnt, status] + [s.reshape(1) for s in u['status']]).cpu().numpy()      # the one read
+    host = torch.cat([n_kept, gt_cnt] + [s.reshape(1) for s in words]).cpu().numpy()                    # the one read
     if host[B + 1]:
         raise Dfu3dError("prepare_batch: status %d (%s)" % (host[B + 1], st.aug_status_message(int(host[B + 1]))))
-    if len(host) > B + 2 and host[B + 2]:
+    if u['status'] and host[B + 2]:
         raise Dfu3dError("prepare_batch: gt_sample status %d" % host[B + 2])
+    if k is not None and host[-1]:
+        raise Dfu3dError("prepare_batch: sample_points status %d (%s)"
+                         % (host[-1], point_sample_ops.status_message(int(host[-1]))))
     batch.update(points=out[:int(host[0])], gt_boxes=gt[:, :int(host[1:B + 1].max())].contiguous(),
                  point_cnt=point_cnt, empty_scenes=[b for b in range(B) if host[1 + b] == 0])
     return batch

@@ -1,24 +1,30 @@
-"""Row f-10: OpenPCDet's DataProcessor for the dynamic-pillar CenterPoint configuration --
+"""Rows f-10 and f-18: OpenPCDet's DataProcessor for the dynamic-pillar CenterPoint configuration --
 `mask_points_and_boxes_outside_range`, `shuffle_points`, `transform_points_to_voxels_placeholder` -- with the range
-masks on the GPU (dfu3d_world_aug_collate, include/dfu3d_aug.h).
+masks on the GPU (dfu3d_world_aug_collate, include/dfu3d_aug.h), and PointRCNN's `sample_points` (NUM_POINTS per scene)
+on the GPU (dfu3d_sample_points, csrc/dfu3d_smp.h).
 
-Reference: pcdet/datasets/processor/data_processor.py (`__init__` :64-77, :79-115), common_utils.mask_points_by_range,
-box_utils.mask_boxes_outside_range_numpy.
+Reference: pcdet/datasets/processor/data_processor.py (`__init__` :64-77, :79-115, sample_points :182-214),
+common_utils.mask_points_by_range, box_utils.mask_boxes_outside_range_numpy.
 
 `forward(data_dict)` is the per-scene form, NumPy in and out; the batched form is data_augmentor.prepare_batch, which
 asks this object for the range and for what to mask.  Divergences: `transform_points_to_voxels`
 and every other entry raise NotImplementedError at construction (the voxels of this configuration are made by
-DynamicPillarVFE on the device); USE_CENTER_TO_FILTER false raises; the batched form does not shuffle.
+DynamicPillarVFE on the device); USE_CENTER_TO_FILTER false raises; the batched form does not shuffle.  sample_points
+(DESIGN.md row f-18): the random words come from torch's generator of the device and not from NumPy's; equal words are
+ordered by the row index; the rows a short scene repeats are drawn by a multiply-shift; a scene without points raises
+Dfu3dError here and sets a status bit in the batched form; the entry needs NUM_POINTS and a range mask before it.
 """
 from functools import partial
 
 import numpy as np
 import torch
 
+from .. import point_sample_ops as smp
 from .. import stages as st
 from .._lib import Dfu3dError
 
-SUPPORTED = ('mask_points_and_boxes_outside_range', 'shuffle_points', 'transform_points_to_voxels_placeholder')
+SUPPORTED = ('mask_points_and_boxes_outside_range', 'shuffle_points', 'transform_points_to_voxels_placeholder',
+             'sample_points')
 
 
 class DataProcessor(object):
@@ -33,6 +39,7 @@ class DataProcessor(object):
         self.device = torch.device(device)
         self.data_processor_queue = []
         self._mask_cfg = None
+        self._sample_cfg = None
         self._range = None
         for cur_cfg in processor_configs:
             name = cur_cfg['NAME']
@@ -47,6 +54,13 @@ class DataProcessor(object):
             return 0
         boxes = self._mask_cfg.get('REMOVE_OUTSIDE_BOXES', False) and self.training
         return st.AUG_MASK_POINTS | (st.AUG_MASK_BOXES if boxes else 0)
+
+    def sample_count(self):
+        """The rows per scene `sample_points` makes in this mode; None without the entry or where it says -1."""
+        if self._sample_cfg is None:
+            return None
+        k = int(self._sample_cfg['NUM_POINTS'][self.mode])
+        return None if k == -1 else k
 
     def range_tensor(self):
         if self._range is None:
@@ -99,6 +113,32 @@ class DataProcessor(object):
             points = data_dict['points']
             shuffle_idx = np.random.permutation(points.shape[0])
             data_dict['points'] = points[shuffle_idx]
+        return data_dict
+
+    def sample_points(self, data_dict=None, config=None):
+        if data_dict is None:
+            if 'NUM_POINTS' not in config:
+                raise NotImplementedError("sample_points: NUM_POINTS is required")
+            if self._mask_cfg is None:
+                raise NotImplementedError("sample_points: the entry must come after mask_points_and_boxes_outside_range "
+                                          "(the batched form samples what the range mask keeps)")
+            k = int(config['NUM_POINTS'][self.mode])
+            if k != -1 and not 1 <= k <= smp.MAX_OUT:
+                raise Dfu3dError("sample_points: NUM_POINTS %d (-1, or 1 .. %d)" % (k, smp.MAX_OUT))
+            self._sample_cfg = config
+            return partial(self.sample_points, config=config)
+        k = self.sample_count()
+        if k is None:
+            return data_dict
+        points = data_dict['points']
+        if points.ndim != 2 or points.dtype != np.float32 or points.shape[1] < 3:
+            raise Dfu3dError("sample_points: points must be (n, C >= 3) float32")
+        n = points.shape[0]
+        if n == 0:
+            raise Dfu3dError("sample_points: a scene without points")
+        block = torch.from_numpy(np.concatenate([np.zeros((n, 1), np.float32), points], 1)).to(self.device)
+        out, _ = smp.sample_points(block, torch.full((1,), n, dtype=torch.int32, device=self.device), k)
+        data_dict['points'] = out[:, 1:].cpu().numpy()
         return data_dict
 
     def transform_points_to_voxels_placeholder(self, data_dict=None, config=None):

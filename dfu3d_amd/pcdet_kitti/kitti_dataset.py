@@ -339,9 +339,19 @@ class KittiDataset(object):
         if enc is None:
             return _Encoder(4)
         used, src = list(_get(enc, 'used_feature_list')), list(_get(enc, 'src_feature_list'))
-        if used != src or len(used) != 4:
-            raise NotImplementedError("KittiDataset: POINT_FEATURE_ENCODING must keep the four columns of the file as they are")
+        cut = self._samples() and 3 <= len(used) < 4 and used == src[:len(used)]      # sample_points copies a prefix
+        if len(src) != 4 or not (used == src or cut):
+            raise NotImplementedError("KittiDataset: POINT_FEATURE_ENCODING must keep the four columns of the file as they "
+                                      "are (or, with a sample_points entry, their first three)")
         return _Encoder(len(used))
+
+    def _samples(self):
+        """The DATA_PROCESSOR has a sample_points entry that samples in this mode."""
+        for entry in _get(self.dataset_cfg, 'DATA_PROCESSOR', None) or []:
+            if _get(entry, 'NAME') == 'sample_points':
+                num = _get(entry, 'NUM_POINTS', None)
+                return num is not None and _get(num, self.mode) != -1
+        return False
 
     @property
     def point_cloud_range(self):
