@@ -20,6 +20,7 @@ sampler's batch draw.
 import numpy as np
 import torch
 
+from .. import hard_voxel_ops
 from .. import point_sample_ops
 from .. import stages as st
 from .._lib import Dfu3dError
@@ -279,7 +280,8 @@ def _pack_sampled(sampler, data_dicts, class_names, device):
     }
 
 
-def prepare_batch(data_dicts, augmentor, processor, class_names, training=True, as_padded=False):
+def prepare_batch(data_dicts, augmentor, processor, class_names, training=True, as_padded=False,
+                  voxel_features_only=False):
     """B scenes -> the model's batch_dict on the device: `points` (sum n, 1 + C) with the batch index in column 0,
     `gt_boxes` (B, max_gt, 8|10) zero-padded with the class id last, `batch_size`, `gt_cnt` (B).
 
@@ -294,7 +296,13 @@ def prepare_batch(data_dicts, augmentor, processor, class_names, training=True, 
     A processor with a `sample_points` entry (processor.sample_count()): what the range mask kept of every scene goes
     through point_sample_ops.sample_points, so `points` is (B * K, 1 + processor.num_point_features) in both forms and
     `point_cnt` is K for every scene; a scene the mask left without points raises in the default form (the same one
-    read) and sets DFU3D_SMP_EMPTY_SCENE in the last word of `status` in the padded form."""
+    read) and sets DFU3D_SMP_EMPTY_SCENE in its word of `status` in the padded form.
+    A processor with a `transform_points_to_voxels` entry (processor.voxel_config()): what the mask, and the sampling if
+    there is one, left goes through hard_voxel_ops.hard_voxels in the order it arrives; the batch gains `voxels` (V, T, C),
+    `voxel_coords` (V, 4) [b, z, y, x], `voxel_num_points` (V) and `voxel_cnt` (B), and `points` stays.  Default form:
+    V = n_voxels, which joins the one read, as does the stage's status word (checked last).  Padded form: V = V_cap,
+    `n_voxels` is a device tensor and the status word is the last of `status`.  voxel_features_only=True: `voxel_features`
+    (V, C), the mean of every voxel's rows (what MeanVFE makes of `voxels`, the same bits), instead of `voxels`."""
     B = len(data_dicts)
     if B == 0:
         raise Dfu3dError("prepare_batch: no scenes")
@@ -323,10 +331,24 @@ def prepare_batch(data_dicts, augmentor, processor, class_names, training=True, 
         n_kept = torch.full((1,), B * k, dtype=torch.int32, device=device)
         point_cnt = torch.full((B,), k, dtype=torch.int32, device=device)
         words.append(sampled)
+    vc = processor.voxel_config()
+    if vc is not None:                                     # what is left of every scene -> its voxels
+        cols = min(processor.num_point_features, out.shape[1] - 1)
+        hv = hard_voxel_ops.hard_voxels(out, point_cnt, processor.point_cloud_range, vc['voxel_size'], vc['grid_size'],
+                                        vc['max_points'], vc['max_voxels'], out_cols=cols,
+                                        want_voxels=not voxel_features_only, want_mean=voxel_features_only)
+        vox = {'voxel_coords': hv.voxel_coords, 'voxel_num_points': hv.voxel_num_points}
+        vox.update({'voxel_features': hv.voxel_mean} if voxel_features_only else {'voxels': hv.voxels})
+        batch['voxel_cnt'] = hv.voxel_cnt
     if as_padded:
         batch.update(points=out, gt_boxes=gt, n_kept=n_kept, point_cnt=point_cnt, status=words)
+        if vc is not None:
+            batch.update(vox, n_voxels=hv.n_voxels, status=words + [hv.status])
         return batch
-    host = torch.cat([n_kept, gt_cnt] + [s.reshape(1) for s in words]).cpu().numpy()                    # the one read
+    tail = [hv.status, hv.n_voxels] if vc is not None else []
+    host = torch.cat([n_kept, gt_cnt] + [s.reshape(1) for s in words + tail]).cpu().numpy()             # the one read
+    if vc is not None:
+        host, (hv_status, n_vox) = host[:-2], (int(host[-2]), int(host[-1]))
     if host[B + 1]:
         raise Dfu3dError("prepare_batch: status %d (%s)" % (host[B + 1], st.aug_status_message(int(host[B + 1]))))
     if u['status'] and host[B + 2]:
@@ -334,6 +356,11 @@ def prepare_batch(data_dicts, augmentor, processor, class_names, training=True, 
     if k is not None and host[-1]:
         raise Dfu3dError("prepare_batch: sample_points status %d (%s)"
                          % (host[-1], point_sample_ops.status_message(int(host[-1]))))
+    if vc is not None:
+        if hv_status:
+            raise Dfu3dError("prepare_batch: transform_points_to_voxels status %d (%s)"
+                             % (hv_status, hard_voxel_ops.status_message(hv_status)))
+        batch.update({key: t[:n_vox] for key, t in vox.items()})
     batch.update(points=out[:int(host[0])], gt_boxes=gt[:, :int(host[1:B + 1].max())].contiguous(),
                  point_cnt=point_cnt, empty_scenes=[b for b in range(B) if host[1 + b] == 0])
     return batch

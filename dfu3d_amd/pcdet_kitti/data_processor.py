@@ -1,15 +1,17 @@
-"""Rows f-10 and f-18: OpenPCDet's DataProcessor for the dynamic-pillar CenterPoint configuration --
+"""Rows f-10, f-18 and f-19: OpenPCDet's DataProcessor for the dynamic-pillar CenterPoint configuration --
 `mask_points_and_boxes_outside_range`, `shuffle_points`, `transform_points_to_voxels_placeholder` -- with the range
-masks on the GPU (dfu3d_world_aug_collate, include/dfu3d_aug.h), and PointRCNN's `sample_points` (NUM_POINTS per scene)
-on the GPU (dfu3d_sample_points, csrc/dfu3d_smp.h).
+masks on the GPU (dfu3d_world_aug_collate, include/dfu3d_aug.h), PointRCNN's `sample_points` (NUM_POINTS per scene)
+on the GPU (dfu3d_sample_points, csrc/dfu3d_smp.h), and the voxel models' `transform_points_to_voxels` (hard voxels)
+on the GPU (dfu3d_hard_voxels, csrc/dfu3d_hvox.h).
 
-Reference: pcdet/datasets/processor/data_processor.py (`__init__` :64-77, :79-115, sample_points :182-214),
+Reference: pcdet/datasets/processor/data_processor.py (`__init__` :64-77, :79-115, :133-180, sample_points :182-214),
 common_utils.mask_points_by_range, box_utils.mask_boxes_outside_range_numpy.
 
 `forward(data_dict)` is the per-scene form, NumPy in and out; the batched form is data_augmentor.prepare_batch, which
-asks this object for the range and for what to mask.  Divergences: `transform_points_to_voxels`
-and every other entry raise NotImplementedError at construction (the voxels of this configuration are made by
-DynamicPillarVFE on the device); USE_CENTER_TO_FILTER false raises; the batched form does not shuffle.  sample_points
+asks this object for the range and for what to mask.  Divergences: every other entry raises
+NotImplementedError at construction; USE_CENTER_TO_FILTER false raises; the batched form does not shuffle.
+transform_points_to_voxels: the voxel generator is the rule of csrc/dfu3d_hvox.h in float32; it needs
+MAX_POINTS_PER_VOXEL and MAX_NUMBER_OF_VOXELS (NotImplementedError without them, and for DOUBLE_FLIP).  sample_points
 (DESIGN.md row f-18): the random words come from torch's generator of the device and not from NumPy's; equal words are
 ordered by the row index; the rows a short scene repeats are drawn by a multiply-shift; a scene without points raises
 Dfu3dError here and sets a status bit in the batched form; the entry needs NUM_POINTS and a range mask before it.
@@ -19,12 +21,13 @@ from functools import partial
 import numpy as np
 import torch
 
+from .. import hard_voxel_ops as hvox
 from .. import point_sample_ops as smp
 from .. import stages as st
 from .._lib import Dfu3dError
 
 SUPPORTED = ('mask_points_and_boxes_outside_range', 'shuffle_points', 'transform_points_to_voxels_placeholder',
-             'sample_points')
+             'sample_points', 'transform_points_to_voxels')
 
 
 class DataProcessor(object):
@@ -40,6 +43,7 @@ class DataProcessor(object):
         self.data_processor_queue = []
         self._mask_cfg = None
         self._sample_cfg = None
+        self._voxel_cfg = None
         self._range = None
         for cur_cfg in processor_configs:
             name = cur_cfg['NAME']
@@ -61,6 +65,15 @@ class DataProcessor(object):
             return None
         k = int(self._sample_cfg['NUM_POINTS'][self.mode])
         return None if k == -1 else k
+
+    def voxel_config(self):
+        """What `transform_points_to_voxels` makes in this mode: {'voxel_size', 'grid_size', 'max_points', 'max_voxels'};
+        None without the entry."""
+        if self._voxel_cfg is None:
+            return None
+        return {'voxel_size': list(self.voxel_size), 'grid_size': [int(g) for g in self.grid_size],
+                'max_points': int(self._voxel_cfg['MAX_POINTS_PER_VOXEL']),
+                'max_voxels': int(self._voxel_cfg['MAX_NUMBER_OF_VOXELS'][self.mode])}
 
     def range_tensor(self):
         if self._range is None:
@@ -147,6 +160,41 @@ class DataProcessor(object):
             self.grid_size = np.round(grid_size).astype(np.int64)
             self.voxel_size = config['VOXEL_SIZE']
             return partial(self.transform_points_to_voxels_placeholder, config=config)
+        return data_dict
+
+    def transform_points_to_voxels(self, data_dict=None, config=None):
+        if data_dict is None:
+            if 'MAX_POINTS_PER_VOXEL' not in config or 'MAX_NUMBER_OF_VOXELS' not in config:
+                raise NotImplementedError("transform_points_to_voxels: MAX_POINTS_PER_VOXEL and MAX_NUMBER_OF_VOXELS are "
+                                          "required")
+            if config.get('DOUBLE_FLIP', False):
+                raise NotImplementedError("transform_points_to_voxels: DOUBLE_FLIP is not supported")
+            grid_size = (self.point_cloud_range[3:6] - self.point_cloud_range[0:3]) / np.array(config['VOXEL_SIZE'])
+            self.grid_size = np.round(grid_size).astype(np.int64)
+            self.voxel_size = config['VOXEL_SIZE']
+            t, v = int(config['MAX_POINTS_PER_VOXEL']), int(config['MAX_NUMBER_OF_VOXELS'][self.mode])
+            if not 1 <= t <= hvox.MAX_POINTS or v < 1:
+                raise Dfu3dError("transform_points_to_voxels: MAX_POINTS_PER_VOXEL %d (1 .. %d), MAX_NUMBER_OF_VOXELS %d "
+                                 "(1 or more)" % (t, hvox.MAX_POINTS, v))
+            self._voxel_cfg = config
+            return partial(self.transform_points_to_voxels, config=config)
+        points = data_dict['points']
+        if points.ndim != 2 or points.dtype != np.float32 or points.shape[1] < 3:
+            raise Dfu3dError("transform_points_to_voxels: points must be (n, C >= 3) float32")
+        n, vc = points.shape[0], self.voxel_config()
+        block = torch.from_numpy(np.concatenate([np.zeros((n, 1), np.float32), points], 1)).to(self.device)
+        out = hvox.hard_voxels(block, torch.full((1,), n, dtype=torch.int32, device=self.device), self.point_cloud_range,
+                               vc['voxel_size'], vc['grid_size'], vc['max_points'], vc['max_voxels'])
+        host = torch.cat([out.n_voxels, out.status]).cpu().numpy()
+        if host[1]:
+            raise Dfu3dError("transform_points_to_voxels: status %d (%s)" % (host[1], hvox.status_message(int(host[1]))))
+        nv = int(host[0])
+        voxels = out.voxels[:nv].cpu().numpy()
+        if not data_dict.get('use_lead_xyz', True):
+            voxels = voxels[..., 3:]                                # remove xyz in voxels(N, 3)
+        data_dict['voxels'] = voxels
+        data_dict['voxel_coords'] = out.voxel_coords[:nv, 1:].cpu().numpy()
+        data_dict['voxel_num_points'] = out.voxel_num_points[:nv].cpu().numpy()
         return data_dict
 
     def forward(self, data_dict):
