@@ -6,7 +6,11 @@
 `forward(batch_dict)` in training returns ({'loss': loss}, tb_dict, disp_dict) with tb_dict['loss_rpn'] (tb_dict is
 read from the device in one copy); in evaluation (pred_dicts, recall_dict).  Module names of the config this package
 does not have (a BACKBONE_3D, PFE, POINT_HEAD, ROI_HEAD entry, another VFE / MAP_TO_BEV / BACKBONE_2D / DENSE_HEAD name)
-raise NotImplementedError naming them."""
+raise NotImplementedError naming them.
+
+`CenterPoint(..., sparse_3d=True)` is the voxel model of cfgs/kitti_models/centerpoint.yaml: `vfe` (MeanVFE) ->
+`backbone_3d` (VoxelBackBone8x / VoxelResBackBone8x on the sparse convolution stage) -> `map_to_bev_module`
+(HeightCompression) -> `backbone_2d` -> `dense_head`.  Without the keyword those names raise as before."""
 import os
 
 import torch
@@ -16,7 +20,11 @@ from . import iou3d_nms_utils
 from .base_bev_backbone import BaseBEVBackbone
 from .center_head_module import CenterHeadModule
 from .dynamic_pillar_vfe import DynamicPillarVFE, DynamicPillarVFESimple2D
+from .height_compression import HeightCompression
+from .mean_vfe import MeanVFE
 from .pointpillar_scatter import PointPillarScatter, PointPillarScatter3d
+from .spconv_backbone import VoxelBackBone8x, VoxelResBackBone8x
+from .spconv_utils import find_all_spconv_keys
 
 
 def _get(cfg, key, *default):
@@ -33,6 +41,12 @@ MODULES = {
     'DENSE_HEAD': {'CenterHead': CenterHeadModule},
 }
 ABSENT = ('BACKBONE_3D', 'PFE', 'POINT_HEAD', 'ROI_HEAD')
+# what sparse_3d=True adds
+SPARSE_MODULES = {
+    'VFE': {'MeanVFE': MeanVFE},
+    'BACKBONE_3D': {'VoxelBackBone8x': VoxelBackBone8x, 'VoxelResBackBone8x': VoxelResBackBone8x},
+    'MAP_TO_BEV': {'HeightCompression': HeightCompression},
+}
 
 
 class _Dataset:
@@ -40,21 +54,39 @@ class _Dataset:
         self.__dict__.update(kw)
 
 
-def _module_class(model_cfg, section):
+def _module_class(model_cfg, section, sparse_3d=False):
     cfg = _get(model_cfg, section, None)
     if cfg is None:
         return None, None
     name = _get(cfg, 'NAME')
-    if name not in MODULES[section]:
+    known = dict(MODULES.get(section, {}), **(SPARSE_MODULES.get(section, {}) if sparse_3d else {}))
+    if name not in known:
         raise NotImplementedError("CenterPoint: %s.NAME = %r is not part of this package (it has %s)"
-                                  % (section, name, ", ".join(sorted(MODULES[section]))))
-    return cfg, MODULES[section][name]
+                                  % (section, name, ", ".join(sorted(known))))
+    return cfg, known[name]
+
+
+def adapt_spconv_weights(model, model_state):
+    """detector3d_template.py _load_state_dict: a sparse convolution's weight in the 1.x layout (k, k, k, Cin, Cout)
+    becomes the model's (Cout, k, k, k, Cin), by the transpose of the last two axes or by the permutation, whichever
+    gives the parameter's shape; everything else is passed on as it is."""
+    own, keys, out = model.state_dict(), find_all_spconv_keys(model), {}
+    for key, val in model_state.items():
+        if key in keys and key in own and own[key].shape != val.shape:
+            native = val.transpose(-1, -2)
+            if native.shape == own[key].shape:
+                val = native.contiguous()
+            elif val.dim() == 5 and val.permute(4, 0, 1, 2, 3).shape == own[key].shape:
+                val = val.permute(4, 0, 1, 2, 3).contiguous()
+        out[key] = val
+    return out
 
 
 class CenterPoint(nn.Module):
-    def __init__(self, model_cfg, num_class, dataset=None, **kwargs):
+    def __init__(self, model_cfg, num_class, dataset=None, sparse_3d=False, **kwargs):
         """dataset: an object with class_names, grid_size, point_cloud_range, voxel_size and
-        point_feature_encoder.num_point_features -- or the same as keywords (num_point_features for the last)."""
+        point_feature_encoder.num_point_features -- or the same as keywords (num_point_features for the last).
+        sparse_3d: accept MeanVFE, a BACKBONE_3D (VoxelBackBone8x, VoxelResBackBone8x) and HeightCompression."""
         super().__init__()
         if dataset is None:
             feats = kwargs.pop('num_point_features')
@@ -64,7 +96,7 @@ class CenterPoint(nn.Module):
         self.dataset = dataset
         self.class_names = list(dataset.class_names)
         self.register_buffer('global_step', torch.LongTensor(1).zero_())
-        absent = [s for s in ABSENT if _get(model_cfg, s, None)]
+        absent = [s for s in ABSENT if _get(model_cfg, s, None) and not (sparse_3d and s == 'BACKBONE_3D')]
         if absent:
             raise NotImplementedError("CenterPoint: the config's %s is not part of this package" % ", ".join(absent))
         grid_size = [int(v) for v in dataset.grid_size]
@@ -72,13 +104,23 @@ class CenterPoint(nn.Module):
         voxel_size = [float(v) for v in dataset.voxel_size]
         self.module_list = []
         num_bev = None
-        cfg, cls = _module_class(model_cfg, 'VFE')
+        cfg, cls = _module_class(model_cfg, 'VFE', sparse_3d)
         self.vfe = None
+        num_point_features = dataset.point_feature_encoder.num_point_features
         if cls is not None:
-            self.vfe = cls(model_cfg=cfg, num_point_features=dataset.point_feature_encoder.num_point_features,
+            self.vfe = cls(model_cfg=cfg, num_point_features=num_point_features,
                            point_cloud_range=pc_range, voxel_size=voxel_size, grid_size=grid_size)
             self.module_list.append(self.vfe)
-        cfg, cls = _module_class(model_cfg, 'MAP_TO_BEV')
+        if sparse_3d:
+            cfg, cls = _module_class(model_cfg, 'BACKBONE_3D', True)
+            self.backbone_3d = None
+            if cls is not None:
+                if isinstance(self.vfe, MeanVFE):
+                    num_point_features = self.vfe.get_output_feature_dim()
+                self.backbone_3d = cls(model_cfg=cfg, input_channels=num_point_features, grid_size=grid_size,
+                                       voxel_size=voxel_size, point_cloud_range=pc_range)
+                self.module_list.append(self.backbone_3d)
+        cfg, cls = _module_class(model_cfg, 'MAP_TO_BEV', sparse_3d)
         self.map_to_bev_module = None
         if cls is not None:
             self.map_to_bev_module = cls(model_cfg=cfg, grid_size=grid_size)
@@ -155,12 +197,16 @@ class CenterPoint(nn.Module):
             recall_dict['gt'] += gt.shape[0]
         return recall_dict
 
+    def adapt_spconv_weights(self, model_state):
+        return adapt_spconv_weights(self, model_state)
+
     def load_params_from_file(self, filename, to_cpu=False, logger=None):
-        """checkpoint['model_state'] into this model, strict: every key and shape must be this model's."""
+        """checkpoint['model_state'] into this model, strict: every key and shape must be this model's (a sparse
+        convolution's weight may come in the 1.x layout: adapt_spconv_weights)."""
         if not os.path.isfile(filename):
             raise FileNotFoundError(filename)
         checkpoint = torch.load(filename, map_location=torch.device('cpu') if to_cpu else None)
-        self.load_state_dict(checkpoint['model_state'], strict=True)
+        self.load_state_dict(adapt_spconv_weights(self, checkpoint['model_state']), strict=True)
         if logger is not None:
             logger.info('==> Loaded %d tensors from %s' % (len(checkpoint['model_state']), filename))
         return checkpoint

@@ -143,6 +143,9 @@ class KittiDataset(object):
         self.root_split_path = self.root_path
         self.kitti_infos = []
         self._augmentor = self._processor = None
+        # `batches` with a transform_points_to_voxels entry: True hands the model `voxel_features` (the voxel means, what
+        # MeanVFE -> a sparse backbone reads) in place of the (V, T, C) block `voxels`
+        self.voxel_features_only = False
         self.set_split(_get(_get(dataset_cfg, 'DATA_SPLIT'), self.mode))
         self.include_kitti_data(self.mode)
 
@@ -409,7 +412,8 @@ class KittiDataset(object):
         if self.training and has_boxes and self.data_augmentor is not None and self.data_augmentor.sampler is not None:
             for x in dicts:
                 x['gt_boxes_mask'] = np.ones(len(x['gt_boxes']), dtype=np.bool_)
-        batch = prepare_batch(dicts, self.data_augmentor, self.data_processor, self.class_names, training=self.training)
+        batch = prepare_batch(dicts, self.data_augmentor, self.data_processor, self.class_names, training=self.training,
+                              voxel_features_only=self.voxel_features_only)
         if not has_boxes:
             for k in ('gt_boxes', 'gt_cnt', 'empty_scenes'):
                 batch.pop(k, None)
