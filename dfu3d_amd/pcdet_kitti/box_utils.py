@@ -97,3 +97,31 @@ def boxes_to_corners_3d(boxes3d):
     corners = boxes3d[:, None, 3:6].repeat(1, 8, 1) * half[None, :, :]
     corners = rotate_points_along_z(corners.view(-1, 8, 3), boxes3d[:, 6]).view(-1, 8, 3)
     return corners + boxes3d[:, None, 0:3]
+
+
+def boxes_iou_normal(boxes_a, boxes_b):
+    """(N, 4), (M, 4) [x1, y1, x2, y2] torch -> (N, M): overlap over clamp_min(union, 1e-6) (box_utils.py:291-311)."""
+    import torch
+    assert boxes_a.shape[1] == boxes_b.shape[1] == 4
+    x_len = torch.clamp_min(torch.min(boxes_a[:, 2, None], boxes_b[None, :, 2])
+                            - torch.max(boxes_a[:, 0, None], boxes_b[None, :, 0]), min=0)
+    y_len = torch.clamp_min(torch.min(boxes_a[:, 3, None], boxes_b[None, :, 3])
+                            - torch.max(boxes_a[:, 1, None], boxes_b[None, :, 1]), min=0)
+    area_a = (boxes_a[:, 2] - boxes_a[:, 0]) * (boxes_a[:, 3] - boxes_a[:, 1])
+    area_b = (boxes_b[:, 2] - boxes_b[:, 0]) * (boxes_b[:, 3] - boxes_b[:, 1])
+    overlap = x_len * y_len
+    return overlap / torch.clamp_min(area_a[:, None] + area_b[None, :] - overlap, min=1e-6)
+
+
+def boxes3d_lidar_to_aligned_bev_boxes(boxes3d):
+    """(N, 7 + C) torch -> (N, 4) [x1, y1, x2, y2]: the footprint turned to the nearer axis (box_utils.py:314-325)."""
+    import torch
+    from .common_utils import limit_period
+    turn = limit_period(boxes3d[:, 6], offset=0.5, period=np.pi).abs()
+    dims = torch.where(turn[:, None] < np.pi / 4, boxes3d[:, [3, 4]], boxes3d[:, [4, 3]])
+    return torch.cat((boxes3d[:, 0:2] - dims / 2, boxes3d[:, 0:2] + dims / 2), dim=1)
+
+
+def boxes3d_nearest_bev_iou(boxes_a, boxes_b):
+    """(N, 7), (M, 7) torch -> (N, M): the IoU of the axis-aligned footprints (box_utils.py:328-340)."""
+    return boxes_iou_normal(boxes3d_lidar_to_aligned_bev_boxes(boxes_a), boxes3d_lidar_to_aligned_bev_boxes(boxes_b))

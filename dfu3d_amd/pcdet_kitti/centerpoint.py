@@ -54,15 +54,17 @@ class _Dataset:
         self.__dict__.update(kw)
 
 
-def _module_class(model_cfg, section, sparse_3d=False):
+def _module_class(model_cfg, section, sparse_3d=False, more=None, who="CenterPoint"):
+    """more: {section: {name: class}} a detector built on this assembly accepts on top (SECONDNet: its dense head)."""
     cfg = _get(model_cfg, section, None)
     if cfg is None:
         return None, None
     name = _get(cfg, 'NAME')
     known = dict(MODULES.get(section, {}), **(SPARSE_MODULES.get(section, {}) if sparse_3d else {}))
+    known.update((more or {}).get(section, {}))
     if name not in known:
-        raise NotImplementedError("CenterPoint: %s.NAME = %r is not part of this package (it has %s)"
-                                  % (section, name, ", ".join(sorted(known))))
+        raise NotImplementedError("%s: %s.NAME = %r is not part of this package (it has %s)"
+                                  % (who, section, name, ", ".join(sorted(known))))
     return cfg, known[name]
 
 
@@ -83,6 +85,8 @@ def adapt_spconv_weights(model, model_state):
 
 
 class CenterPoint(nn.Module):
+    MORE_MODULES = {}                # what a subclass accepts on top of MODULES / SPARSE_MODULES
+
     def __init__(self, model_cfg, num_class, dataset=None, sparse_3d=False, **kwargs):
         """dataset: an object with class_names, grid_size, point_cloud_range, voxel_size and
         point_feature_encoder.num_point_features -- or the same as keywords (num_point_features for the last).
@@ -132,7 +136,7 @@ class CenterPoint(nn.Module):
             self.backbone_2d = cls(model_cfg=cfg, input_channels=num_bev)
             num_bev = self.backbone_2d.num_bev_features
             self.module_list.append(self.backbone_2d)
-        cfg, cls = _module_class(model_cfg, 'DENSE_HEAD')
+        cfg, cls = _module_class(model_cfg, 'DENSE_HEAD', more=self.MORE_MODULES, who=type(self).__name__)
         self.dense_head = None
         if cls is not None:
             self.dense_head = cls(

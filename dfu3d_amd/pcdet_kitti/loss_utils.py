@@ -6,8 +6,8 @@ Divergence from the reference: `FocalLossCenterNet.forward` takes the heat map's
 clamp(sigmoid(x), 1e-4, 1 - 1e-4) itself (the reference's head does that before it calls the module).  Sums are fp64
 with a fixed shape, so two runs give the same bits.
 
-The losses of PointRCNN's two heads -- `SigmoidFocalClassificationLoss`, `WeightedSmoothL1Loss` and
-`get_corner_loss_lidar` -- are plain torch with autograd, every float operation the reference's in its order; a fused
+The losses of PointRCNN's two heads and of the anchor head -- `SigmoidFocalClassificationLoss`, `WeightedSmoothL1Loss`,
+`WeightedCrossEntropyLoss` and `get_corner_loss_lidar` -- are plain torch with autograd, every float operation the reference's in its order; a fused
 kernel for them in the manner of csrc/centerloss_stage.hip is not built."""
 import math
 
@@ -103,3 +103,11 @@ def get_corner_loss_lidar(pred_bbox3d, gt_bbox3d):
     dist = torch.min(torch.norm(pred - box_utils.boxes_to_corners_3d(gt_bbox3d), dim=2),
                      torch.norm(pred - box_utils.boxes_to_corners_3d(turned), dim=2))
     return _smooth_l1(dist, 1.0).mean(dim=1)
+
+
+class WeightedCrossEntropyLoss(nn.Module):
+    """The cross entropy of the logits against the arg max of a one-hot target, times a weight per anchor."""
+
+    def forward(self, input, target, weights):
+        """input, target (B, #anchors, #classes), weights (B, #anchors) -> (B, #anchors)."""
+        return nn.functional.cross_entropy(input.permute(0, 2, 1), target.argmax(dim=-1), reduction='none') * weights
