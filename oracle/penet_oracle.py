@@ -448,15 +448,25 @@ def voxel_down_sample(pts, voxel_size):
     return acc / cnt[:, None]
 
 
+def knn_mean_dist(pts, k):
+    """Mean distance of every point to its min(k, n) nearest points, itself included (the first half of
+    remove_statistical_outlier): squared distances dx*dx; += dy*dy; += dz*dz, the smallest kept in ascending order,
+    their square roots summed in that order and divided by their number.  Returns (n,) float64."""
+    pts = np.ascontiguousarray(pts, np.float64).reshape(-1, 3)
+    n = pts.shape[0]
+    md = np.empty((n,), np.float64)
+    if n:
+        _lib().orc_knn_mean_dist(_p(pts), ctypes.c_int64(n), ctypes.c_int32(k), _p(md))
+    return md
+
+
 def statistical_outlier(pts, nb_neighbors, std_ratio):
     """remove_statistical_outlier: returns kept indices (order preserved)."""
     pts = np.ascontiguousarray(pts, np.float64).reshape(-1, 3)
     n = pts.shape[0]
     if n == 0 or nb_neighbors < 1:
         return np.zeros((0,), np.int64)
-    md = np.empty((n,), np.float64)
-    _lib().orc_knn_mean_dist(_p(pts), ctypes.c_int64(n),
-                             ctypes.c_int32(nb_neighbors), _p(md))
+    md = knn_mean_dist(pts, nb_neighbors)
     valid = n
     cloud_mean = 0.0
     for v in md:                       # std::accumulate order

@@ -286,7 +286,7 @@ def _fuse_segments(seed, cases, far=False):
     return segsA, segsB
 
 
-def _ballquery_fuse_run(st, segsA, segsB, radius=None, alloc=_zeros):
+def _ballquery_fuse_run(st, segsA, segsB, radius=None, alloc=_zeros, C=0.1):
     """dfu3d_ballquery_fuse over the pool A_s | B_s; with `radius`, the radius filter of the B lists without its
     compaction first and then dfu3d_ballquery_fuse_masked.  -> (A bases, B counts after, B bases after, pool after)."""
     # pool layout: A_s then B_s adjacent (as dfu3d_segments_build lays them out)
@@ -306,12 +306,12 @@ def _ballquery_fuse_run(st, segsA, segsB, radius=None, alloc=_zeros):
     tile_off = alloc(2 * S + 2, torch.int32)
     flags = alloc(cap, torch.uint8)
     if radius is None:
-        st.ballquery_fuse(px, py, pz, ta, cnt_a, tb, cnt_b, 0.1, S, cap, tile_off, flags)
+        st.ballquery_fuse(px, py, pz, ta, cnt_a, tb, cnt_b, C, S, cap, tile_off, flags)
     else:
         queue = alloc(st.rf_queue_ints(cap), torch.int32)
         st.radius_filter(px, py, pz, tb, cnt_b, _t(radius), 1, S, cap, tile_off, flags, queue,
                          phases=st.RF_ALL & ~st.RF_COMPACT)
-        st.ballquery_fuse(px, py, pz, ta, cnt_a, tb, cnt_b, 0.1, S, cap, tile_off, flags, masked=True)
+        st.ballquery_fuse(px, py, pz, ta, cnt_a, tb, cnt_b, C, S, cap, tile_off, flags, masked=True)
     torch.cuda.synchronize()
     X = torch.stack([px, py, pz], 1).cpu().numpy()
     return base_a, cnt_b.cpu().numpy(), tb.cpu().numpy(), X
