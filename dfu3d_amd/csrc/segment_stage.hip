@@ -999,7 +999,7 @@ __global__ __launch_bounds__(QT) void k_shadow_build(
 // u = C(1+1e-5)/16 (17 bits per axis, +-409 m for C = 0.1); a cell is 32 units
 // = 2C(1+1e-5) wide.  The instance's LiDAR points (at most 4096) are chained
 // per cell in LDS: head[hash(cell)] -> node -> node ..., a node being ONE 64-bit
-// word (3 x 17-bit quantised coordinate | 13-bit next link), so that a dense
+// word (three bytes of position inside the cell | next link in the high half), so that a dense
 // cell costs one LDS read per point and no probing.  A pseudo point q can only
 // be within C of points whose cells meet [q-C', q+C'] (C' = C(1+1e-6)): at most
 // two cells per axis, and because fp rounding of the quantisation is monotone no
@@ -1028,11 +1028,20 @@ __global__ __launch_bounds__(1024) void k_tile_scan_class(int S, const int *__re
   }, tile_off);
 }
 
-// |a - b| in one instruction (the compiler expands __sad() into subtract, negate, max)
-__device__ __forceinline__ uint32_t sad_u32(uint32_t a, uint32_t b) {
-  uint32_t r;
-  asm("v_sad_u32 %0, %1, %2, 0" : "=v"(r) : "v"(a), "v"(b));
-  return r;
+// The node test.  A node's low word holds the point's position INSIDE its cell, one byte per axis: (i & 31) + 160; the
+// query's word for a cell u holds Q' = q - 32 u + 32 per axis.  One 32-bit subtraction gives (i - q) + 128 in every byte
+// (no byte borrows, see the query side), the xor turns that into the signed quantised difference d, and one signed
+// 4 x 8-bit dot product of the word with itself is dx^2 + dy^2 + dz^2 (the fourth byte is 0 on both sides).
+// A node is tested exactly iff that sum is <= 314: each quantised difference is within 1 (+3e-11) unit of the true one,
+// so the true distance is at least |max(|d| - 1, 0)| units, and C is 16/(1+1e-5) < 16 units: a neighbour has
+// sum max(|d| - 1, 0)^2 <= 257 (258 > 16.06^2 leaves room for the rounding of the quantisation itself), and 314 is the
+// largest sum d^2 over that set (tests/test_ball_packed_bound_host.py enumerates it).
+constexpr uint32_t BALL_NODE_BIAS = 0x00A0A0A0u;                 // 160 per byte
+constexpr unsigned long long BALL_NODE_END = 0x00FFFFFFull;      // node 0, where every chain ends: link 0, bytes that fail
+constexpr uint32_t BALL_D2_MAX = 314u;
+__device__ __forceinline__ uint32_t ball_packed_d2(uint32_t node_bytes, uint32_t query_bytes) {
+  const int u = (int)((node_bytes - query_bytes) ^ 0x00808080u);
+  return (uint32_t)__builtin_amdgcn_sdot4(u, u, 0, false);
 }
 __device__ __forceinline__ uint32_t bh_hash(uint32_t ix, uint32_t iy, uint32_t iz) {
   // cell coordinates are below 2^12: 24-bit multiplies (three v_mul_lo_u32 per cell, eight cells per query, issue at a
@@ -1051,7 +1060,7 @@ __global__ __launch_bounds__(BT) void k_ball_flags(
     const int *__restrict__ cnt_a, const long long *__restrict__ base_b,
     const int *__restrict__ cnt_b, double T, double C, int S, const int *__restrict__ tile_off,
     uint8_t *__restrict__ flags, int masked) {
-  __shared__ unsigned long long s_node[BH_MAX];
+  __shared__ unsigned long long s_node[BH_MAX + 1];      // [0] the end node, [i + 1] LiDAR point i
   __shared__ uint32_t s_head[BH_HEADS];
   __shared__ int s_pending, s_nkept;
   const int ntile = tile_off[S];
@@ -1103,9 +1112,10 @@ __global__ __launch_bounds__(BT) void k_ball_flags(
         }
         const uint32_t ix = (uint32_t)fx, iy = (uint32_t)fy, iz = (uint32_t)fz;
         const uint32_t prev = atomicExch(&s_head[bh_hash(ix >> 5, iy >> 5, iz >> 5) & mask], (uint32_t)i + 1u);
-        s_node[i] = (unsigned long long)ix | ((unsigned long long)iy << 17) |
-                    ((unsigned long long)iz << 34) | ((unsigned long long)prev << 51);
+        s_node[i + 1] = (unsigned long long)(((ix & 31u) | ((iy & 31u) << 8) | ((iz & 31u) << 16)) + BALL_NODE_BIAS) |
+                        ((unsigned long long)(prev * 8u) << 32);      // the link is the next node's byte offset in s_node
       }
+      if (threadIdx.x == 0) s_node[0] = BALL_NODE_END;
       if (too_wide) s_pending = 1;
       if (mine_kept) s_nkept = 1;                   // (plain store, every writer the same value: atomics on one LDS word serialise lane by lane)
       __syncthreads();
@@ -1131,48 +1141,48 @@ __global__ __launch_bounds__(BT) void k_ball_flags(
           const double fqx = floor(x * inv) + OFF, fqy = floor(y * inv) + OFF, fqz = floor(z * inv) + OFF;
           const bool qin = fqx >= 0.0 && fqy >= 0.0 && fqz >= 0.0 && fqx <= 131071.0 && fqy <= 131071.0 && fqz <= 131071.0;
           const int qx = qin ? (int)fqx : 0, qy = qin ? (int)fqy : 0, qz = qin ? (int)fqz : 0;
-          // one node of a chain (word `wv` of node `node`) against the query
-          auto test_node = [&](uint32_t node, unsigned long long wv) {
-            const uint32_t ax = (uint32_t)(wv & 0x1FFFFull), ay = (uint32_t)((wv >> 17) & 0x1FFFFull),
-                           az = (uint32_t)((wv >> 34) & 0x1FFFFull);
-            // each quantised difference is within 1 (+3e-11) unit of the true one, so the
-            // true distance is at least |max(|d|-1, 0)| units, and C is 16/(1+1e-5) < 16 units:
-            // 258 > 16.06^2 leaves room for the rounding of the quantisation itself.
-            // |a - q| by v_sad_u32, the terms capped at 31 (one capped term alone is 961 > 257) so that the squares are
-            // 24-bit multiplies: a 32-bit v_mul_lo_u32 issues at a quarter of the rate, and three of them were 40 % of a
-            // node's 120 clocks -- the node test is what the query phase runs on (tools/ball_timing.py)
-            const uint32_t sx_ = sad_u32(ax, (uint32_t)qx), sy_ = sad_u32(ay, (uint32_t)qy), sz_ = sad_u32(az, (uint32_t)qz);
-            const uint32_t ex_ = min(sx_ ? sx_ - 1u : 0u, 31u), ey_ = min(sy_ ? sy_ - 1u : 0u, 31u),
-                           ez_ = min(sz_ ? sz_ - 1u : 0u, 31u);
-            if (!qin || __umul24(ex_, ex_) + __umul24(ey_, ey_) + __umul24(ez_, ez_) <= 257u) {
-              const int j = (int)node - 1;
-              const double ex = x - px[ba + j], ey = y - py[ba + j], ez = z - pz[ba + j];
-              double d = ex * ex;
-              d += ey * ey;
-              d += ez * ez;
-              if (d < T) found = true;                       // <=> sqrt(d) < C, see dfu3d_ballquery_fuse
+          // The packed test holds when, for every cell u of the walk, q - 32 u lies in [-17, 48] on every axis (always,
+          // up to the clamped ends of the 17 bits: floor(x inv) is within 17 of both ends of the range and a range end
+          // within 31 of its cell's low border).  Then Q' = q - 32 u + 32 is a byte in [15, 80], node byte - Q' lies in
+          // [80, 176] for ANY node (bytes in [160, 191], also those of another cell that shares the slot) and in
+          // [175, 240] for the end node: no byte borrows from its neighbour.  Everything else takes the exact walk below.
+          const int rx0 = qx - 32 * x0, ry0 = qy - 32 * y0, rz0 = qz - 32 * z0;
+          const bool pk = qin && rx0 <= 48 && ry0 <= 48 && rz0 <= 48 &&
+                          qx - 32 * x1 >= -17 && qy - 32 * y1 >= -17 && qz - 32 * z1 >= -17;
+          // a node by its byte offset in s_node, which is what the links hold (no shift per node)
+          auto node_at = [&](uint32_t off) { return *(const unsigned long long *)((const char *)s_node + off); };
+          // the reference's predicate on the fp64 coordinates of the node at byte offset `off`
+          auto test_exact = [&](uint32_t off) {
+            const int j = (int)(off >> 3) - 1;
+            const double ex = x - px[ba + j], ey = y - py[ba + j], ez = z - pz[ba + j];
+            double d = ex * ex;
+            d += ey * ey;
+            d += ez * ez;
+            if (d < T) found = true;                       // <=> sqrt(d) < C, see dfu3d_ballquery_fuse
+          };
+          // walk one chain; `qc` are the query's packed bytes for the chain's cell (ignored unless pk)
+          auto walk_from = [&](uint32_t node, uint32_t qc) {
+            while (node && !found) {
+              const unsigned long long wv = node_at(node);
+              if (!pk || ball_packed_d2((uint32_t)wv, qc) <= BALL_D2_MAX) test_exact(node);
+              node = (uint32_t)(wv >> 32);
             }
           };
-          // walk a chain from `node`, whose word `wv` the caller has read already
-          auto walk_from = [&](uint32_t node, unsigned long long wv) {
-            while (true) {
-              test_node(node, wv);
-              if (found) return;
-              node = (uint32_t)(wv >> 51);
-              if (!node) return;
-              wv = s_node[node - 1u];
-            }
-          };
-          auto walk = [&](uint32_t node) { if (node) walk_from(node, s_node[node - 1u]); };
-          if (x1 - x0 <= 1 && y1 - y0 <= 1 && z1 - z0 <= 1) {
+          if (pk && x1 - x0 <= 1 && y1 - y0 <= 1 && z1 - z0 <= 1) {
             // the usual case, at most 2 x 2 x 2 cells: all eight heads are read before the first chain is walked
             // (one LDS round trip instead of eight in a row -- most cells are empty, the reads were the cost)
-            uint32_t heads[8];
+            uint32_t heads[8], qb[8];
+            // the query's byte per axis for the low cell and for the high one (a cell that is not there reads the end
+            // node, which any byte in [15, 80] rejects)
+            const uint32_t qbx[2] = {(uint32_t)(rx0 + 32), (uint32_t)(x1 > x0 ? rx0 : rx0 + 32)};
+            const uint32_t qby[2] = {(uint32_t)(ry0 + 32) << 8, (uint32_t)(y1 > y0 ? ry0 : ry0 + 32) << 8};
+            const uint32_t qbz[2] = {(uint32_t)(rz0 + 32) << 16, (uint32_t)(z1 > z0 ? rz0 : rz0 + 32) << 16};
 #pragma unroll
             for (int cidx = 0; cidx < 8; cidx++) {
               const int ux = x0 + (cidx & 1), uy = y0 + ((cidx >> 1) & 1), uz = z0 + (cidx >> 2);
               const bool there = ux <= x1 && uy <= y1 && uz <= z1;
               heads[cidx] = there ? s_head[bh_hash((uint32_t)ux, (uint32_t)uy, (uint32_t)uz) & mask] : 0u;
+              qb[cidx] = qbx[cidx & 1] | qby[(cidx >> 1) & 1] | qbz[cidx >> 2];
             }
             // Four chains at a time.  A chain is a run of DEPENDENT LDS reads (the link sits in the node), a dense
             // instance has a hundred LiDAR points per cell, and a query with no neighbour walks all eight chains to
@@ -1184,24 +1194,32 @@ __global__ __launch_bounds__(BT) void k_ball_flags(
               uint32_t nd[4];
               unsigned long long wv[4];
 #pragma unroll
-              for (int c4 = 0; c4 < 4; c4++) { nd[c4] = heads[g4 + c4]; wv[c4] = nd[c4] ? s_node[nd[c4] - 1u] : 0ull; }
+              for (int c4 = 0; c4 < 4; c4++) { nd[c4] = heads[g4 + c4] * 8u; wv[c4] = node_at(nd[c4]); }
+              // A step costs a rejected node no exec-mask region: a chain that has ended reads the end node (offset 0,
+              // link 0, bytes that fail), the four sums meet in one minimum, and only a step with a candidate enters
+              // the exact test.
               while ((nd[0] | nd[1] | nd[2] | nd[3]) != 0u) {
+                uint32_t d2[4];
 #pragma unroll
-                for (int c4 = 0; c4 < 4; c4++)
-                  if (nd[c4]) {
-                    test_node(nd[c4], wv[c4]);
-                    nd[c4] = (uint32_t)(wv[c4] >> 51);
-                  }
-                if (found) break;
+                for (int c4 = 0; c4 < 4; c4++) d2[c4] = ball_packed_d2((uint32_t)wv[c4], qb[g4 + c4]);
+                if (min(min(d2[0], d2[1]), min(d2[2], d2[3])) <= BALL_D2_MAX) {
 #pragma unroll
-                for (int c4 = 0; c4 < 4; c4++) wv[c4] = nd[c4] ? s_node[nd[c4] - 1u] : 0ull;
+                  for (int c4 = 0; c4 < 4; c4++)
+                    if (d2[c4] <= BALL_D2_MAX) test_exact(nd[c4]);
+                  if (found) break;
+                }
+#pragma unroll
+                for (int c4 = 0; c4 < 4; c4++) { nd[c4] = (uint32_t)(wv[c4] >> 32); wv[c4] = node_at(nd[c4]); }
               }
             }
           } else {
+            // a query outside the 17 bits (every node of its chains is tested exactly) or with more than two cells on
+            // an axis (never seen)
             for (int uz = z0; uz <= z1 && !found; uz++)
               for (int uy = y0; uy <= y1 && !found; uy++)
                 for (int ux = x0; ux <= x1 && !found; ux++)
-                  walk(s_head[bh_hash((uint32_t)ux, (uint32_t)uy, (uint32_t)uz) & mask]);
+                  walk_from(s_head[bh_hash((uint32_t)ux, (uint32_t)uy, (uint32_t)uz) & mask] * 8u,
+                            (uint32_t)(qx - 32 * ux + 32) | ((uint32_t)(qy - 32 * uy + 32) << 8) | ((uint32_t)(qz - 32 * uz + 32) << 16));
           }
         }
         flags[bq + q] = found ? 1 : 0;
