@@ -38,7 +38,8 @@ def _deps():
                os.path.join(INCLUDE, "dfu3d_pn2.h"), os.path.join(INCLUDE, "dfu3d_roi.h"),
                os.path.join(INCLUDE, "dfu3d_tgt.h"), os.path.join(CSRC, "dfu3d_prop.h"),
                os.path.join(CSRC, "dfu3d_smp.h"), os.path.join(CSRC, "dfu3d_hvox.h"),
-               os.path.join(CSRC, "dfu3d_spc.h"), os.path.join(CSRC, "dfu3d_anc.h")])
+               os.path.join(CSRC, "dfu3d_spc.h"), os.path.join(CSRC, "dfu3d_anc.h"),
+               os.path.join(CSRC, "dfu3d_stk.h")])
 
 
 def _stale(out):

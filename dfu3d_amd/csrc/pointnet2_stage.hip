@@ -27,6 +27,7 @@
 //   k_pn_check_batch  column 0 of the stacked points against row / points-per-sample.
 #include "common.hpp"
 #include "dfu3d_pn2.h"
+#include "pn2_device.hpp"
 
 #include <math.h>
 
@@ -36,38 +37,11 @@ constexpr int BT = 256;                              // threads per workgroup of
 constexpr int CCH = 16;                              // channels per workgroup of the channel-looping kernels
 constexpr int FPS_BIG_NT = 1024;
 
-__device__ __forceinline__ float sqdist(float ax, float ay, float az, float bx, float by, float bz) {
-  return (ax - bx) * (ax - bx) + (ay - by) * (ay - by) + (az - bz) * (az - bz);
-}
-__device__ __forceinline__ int wave_max_i(int v) { return ~wave_min_i_dpp(~v); }
-__device__ __forceinline__ void status_or(uint32_t st, uint32_t *__restrict__ status) {   // all lanes of the wave call it
-  st = wave_or_u32_dpp(st);
-  if (lane_id() == 0 && st) atomicOr(status, st);
-}
+using pn2::ball_take;
+using pn2::sqdist;
+using pn2::status_or;
 
-// ---- farthest point sampling ------------------------------------------------------------------------------------------
-// The workgroup's pick of a step from the waves' picks (wave-uniform wkey, widx, wx, wy, wz; waves own ascending runs of
-// points, so among equal keys the lowest wave holds the lowest index).  One barrier; the slot alternates with `par`, so
-// a wave that is a step ahead writes the other slot.
-template <int NW>
-__device__ __forceinline__ void fps_exchange(int4 (*s_a)[NW], float (*s_z)[NW], int par, int wkey, int widx, float wx,
-                                             float wy, float wz, int &old, float &x1, float &y1, float &z1) {
-  const int lane = lane_id(), w = threadIdx.x >> 6;
-  if (lane == 0) {
-    s_a[par][w] = make_int4(wkey, widx, __float_as_int(wx), __float_as_int(wy));
-    s_z[par][w] = wz;
-  }
-  __syncthreads();
-  const int4 e = s_a[par][lane & (NW - 1)];
-  const float ez = s_z[par][lane & (NW - 1)];
-  const int bkey = wave_max_i(e.x);
-  const int wsel = __ffsll((unsigned long long)__ballot(e.x == bkey)) - 1;   // < NW: lane l < NW holds wave l's
-  old = __builtin_amdgcn_readlane(e.y, wsel);
-  x1 = __int_as_float(__builtin_amdgcn_readlane(e.z, wsel));
-  y1 = __int_as_float(__builtin_amdgcn_readlane(e.w, wsel));
-  z1 = readlane_f(ez, wsel);
-}
-
+// ---- farthest point sampling (the step itself: pn2_device.hpp) -------------------------------------------------------
 __device__ __forceinline__ void fps_emit(int *__restrict__ idx, float *__restrict__ new_xyz, size_t slot, int old, float x,
                                          float y, float z) {
   if (threadIdx.x == 0) {
@@ -85,57 +59,16 @@ __global__ __launch_bounds__(NT) void k_pn_fps(const float *__restrict__ xyz, in
   static_assert(NW >= 1 && NW <= 16 && (NW & (NW - 1)) == 0, "the waves' slots are read by lane & (NW - 1)");
   __shared__ int4 s_a[2][NW];
   __shared__ float s_z[2][NW];
-  const int b = blockIdx.x, t = threadIdx.x;
+  const int b = blockIdx.x;
   const float *p = xyz + (size_t)b * N * 3;
   float px[PT], py[PT], pz[PT], pm[PT];
-  uint32_t st = 0u;
-#pragma unroll
-  for (int j = 0; j < PT; j++) {
-    const int k = t * PT + j;
-    if (k < N) {
-      px[j] = p[k * 3 + 0];
-      py[j] = p[k * 3 + 1];
-      pz[j] = p[k * 3 + 2];
-      pm[j] = 1e10f;
-      if (!(isfinite(px[j]) && isfinite(py[j]) && isfinite(pz[j]))) st = DFU3D_PN2_ST_BAD_POINT;
-    } else {                                         // no point: a negative minimum never becomes a maximum
-      px[j] = py[j] = pz[j] = 0.0f;
-      pm[j] = -1.0f;
-    }
-  }
-  status_or(st, status);
+  status_or(pn2::fps_load<PT>(p, 3, N, px, py, pz, pm) ? DFU3D_PN2_ST_BAD_POINT : 0u, status);
   int old = 0;
   float x1 = p[0], y1 = p[1], z1 = p[2];
   const size_t out0 = (size_t)b * npoint;
   fps_emit(idx, new_xyz, out0, old, x1, y1, z1);
   for (int s = 1; s < npoint; s++) {
-    int key = -1, bj = 0;
-#pragma unroll
-    for (int j = 0; j < PT; j++) {
-      const float d = sqdist(px[j], py[j], pz[j], x1, y1, z1);
-      float m = pm[j];
-      m = d < m ? d : m;                             // a NaN distance leaves the minimum
-      pm[j] = m;
-      const int kj = __float_as_int(m);
-      if (kj > key) {                                // strict: the lowest index of the thread among equals
-        key = kj;
-        bj = j;
-      }
-    }
-    const int wkey = wave_max_i(key);
-    const int src = __ffsll((unsigned long long)__ballot(key == wkey)) - 1;
-    const int jsel = __builtin_amdgcn_readlane(bj, src);
-    float wx = 0.0f, wy = 0.0f, wz = 0.0f;
-#pragma unroll
-    for (int j = 0; j < PT; j++) {
-      if (j == jsel) {                               // wave-uniform
-        wx = readlane_f(px[j], src);
-        wy = readlane_f(py[j], src);
-        wz = readlane_f(pz[j], src);
-      }
-    }
-    const int widx = ((t & ~63) + src) * PT + jsel;  // >= N only with wkey < 0, which no workgroup picks
-    fps_exchange<NW>(s_a, s_z, s & 1, wkey, widx, wx, wy, wz, old, x1, y1, z1);
+    pn2::fps_step_reg<NW, PT>(px, py, pz, pm, s_a, s_z, s & 1, old, x1, y1, z1);
     fps_emit(idx, new_xyz, out0 + s, old, x1, y1, z1);
   }
 }
@@ -155,41 +88,15 @@ __global__ __launch_bounds__(FPS_BIG_NT) void k_pn_fps_big(const float *__restri
   float x1 = p[0], y1 = p[1], z1 = p[2];
   const size_t out0 = (size_t)b * npoint;
   fps_emit(idx, new_xyz, out0, old, x1, y1, z1);
-  uint32_t st = 0u;
+  bool bad = false;
   for (int s = 1; s < npoint; s++) {
-    int key = -1, bi = 0;
-    float bx = 0.0f, by = 0.0f, bz = 0.0f;
-    for (int k = lo + lane; k < hi; k += 64) {
-      const float x = p[k * 3 + 0], y = p[k * 3 + 1], z = p[k * 3 + 2];
-      float m = 1e10f;
-      if (s == 1) {
-        if (!(isfinite(x) && isfinite(y) && isfinite(z))) st = DFU3D_PN2_ST_BAD_POINT;
-      } else {
-        m = pm[k];
-      }
-      const float d = sqdist(x, y, z, x1, y1, z1);
-      m = d < m ? d : m;
-      pm[k] = m;
-      const int kj = m >= 0.0f ? __float_as_int(m) : 0;      // (a scratch the caller overwrote cannot leave the range)
-      if (kj > key) {
-        key = kj;
-        bi = k;
-        bx = x;
-        by = y;
-        bz = z;
-      }
-    }
-    const int wkey = wave_max_i(key);
-    const int widx = wave_min_i_dpp(key == wkey ? bi : 0x7FFFFFFF);
-    const int src = __ffsll((unsigned long long)__ballot(key == wkey && bi == widx)) - 1;
-    fps_exchange<NW>(s_a, s_z, s & 1, wkey, widx, readlane_f(bx, src), readlane_f(by, src), readlane_f(bz, src), old,
-                     x1, y1, z1);
+    pn2::fps_step_mem<NW>(p, 3, pm, lo, hi, s == 1, bad, s_a, s_z, s & 1, old, x1, y1, z1);
     fps_emit(idx, new_xyz, out0 + s, old, x1, y1, z1);
   }
   if (npoint == 1)                                   // the walk that looks at the coordinates did not run
     for (int k = lo + lane; k < hi; k += 64)
-      if (!(isfinite(p[k * 3 + 0]) && isfinite(p[k * 3 + 1]) && isfinite(p[k * 3 + 2]))) st = DFU3D_PN2_ST_BAD_POINT;
-  status_or(st, status);
+      if (!pn2::finite3(p[k * 3 + 0], p[k * 3 + 1], p[k * 3 + 2])) bad = true;
+  status_or(bad ? DFU3D_PN2_ST_BAD_POINT : 0u, status);
 }
 
 // ---- ball query -------------------------------------------------------------------------------------------------------
@@ -198,18 +105,6 @@ struct BallScale {
   int nsample;
   int *idx;
 };
-
-// the hits of one 64-point tile for one scale; wave-uniform control flow
-__device__ __forceinline__ void ball_take(bool hit, int k, int tile0, int nsample, int *__restrict__ o, int &cnt, int &first,
-                                          bool &full) {
-  const unsigned long long m = __ballot(hit);
-  if (!m) return;
-  if (cnt == 0) first = tile0 + __ffsll(m) - 1;
-  const int rank = cnt + __popcll(m & ((1ull << lane_id()) - 1ull));
-  if (hit && rank < nsample) o[rank] = k;
-  cnt += __popcll(m);
-  full = cnt >= nsample;
-}
 
 __global__ __launch_bounds__(BT) void k_pn_ball(const float *__restrict__ xyz, const float *__restrict__ centres, int N, int M,
                                                 int S, BallScale s0, BallScale s1) {

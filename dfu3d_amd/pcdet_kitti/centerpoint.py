@@ -100,7 +100,8 @@ class CenterPoint(nn.Module):
         self.dataset = dataset
         self.class_names = list(dataset.class_names)
         self.register_buffer('global_step', torch.LongTensor(1).zero_())
-        absent = [s for s in ABSENT if _get(model_cfg, s, None) and not (sparse_3d and s == 'BACKBONE_3D')]
+        absent = [s for s in ABSENT if _get(model_cfg, s, None) and not (sparse_3d and s == 'BACKBONE_3D')
+                  and s not in self.MORE_MODULES]           # (a subclass builds the sections it names itself)
         if absent:
             raise NotImplementedError("CenterPoint: the config's %s is not part of this package" % ", ".join(absent))
         grid_size = [int(v) for v in dataset.grid_size]
