@@ -82,7 +82,7 @@ int dfu3d_stk_fps(const float *xyz, int32_t stride, int64_t rows, const int32_t 
  * (M, nsample_s): the first nsample_s sample-local indices in ascending order with d2 < radius_s * radius_s (strict;
  * the product in float32) among the rows of the centre's OWN sample, the remaining slots the first hit; empty_s uint8
  * (M): 1 for a ball without a hit, whose slots are all 0.  Every element is written.  The sample of a centre is found
- * in cstart; a centre beyond cstart[B] is an empty ball (DFU3D_STK_ST_BAD_COUNT).  N or M may be 0.  n_scales 1 or 2;
+ * in cstart; a centre beyond cstart[B] is an empty ball (DFU3D_STK_ST_BAD_COUNT).  N or M may be 0 (M = 0: nothing is launched, the outputs may be NULL).  n_scales 1 or 2;
  * the arguments of scale 1 are ignored for n_scales = 1.  nsample_s >= 1, radius_s not NaN, else DFU3D_EINVAL. */
 int dfu3d_stk_ball_query(const float *xyz, int32_t stride, int64_t N, const int32_t *start, const float *centres,
                          int32_t cstride, int64_t M, const int32_t *cstart, int32_t B, int32_t n_scales, float radius0,
@@ -102,7 +102,8 @@ int dfu3d_stk_group(const float *xyz, int32_t stride, int64_t N, const int32_t *
 
 /* The index tensor of the grouping backward: gidx int32 (M * nsample) = start[b] + idx, the GLOBAL row of every
  * entry, and -1 for the entries of an empty ball and for an index outside its sample (that one sets
- * DFU3D_STK_ST_BAD_INDEX).  dfu3d_pn2_invert(gidx, 1, N, M * nsample, ...) leaves the -1 entries out and
+ * DFU3D_STK_ST_BAD_INDEX).  A centre beyond cstart[B] sets DFU3D_STK_ST_BAD_COUNT as in dfu3d_stk_group, whatever its
+ * empty flag.  dfu3d_pn2_invert(gidx, 1, N, M * nsample, ...) leaves the -1 entries out and
  * dfu3d_pn2_gather_backward(grad_out + 3 * M * nsample, NULL, csr, list, 1, C, N, ...) sums the rest in ascending entry
  * number: grad_features as (C, N). */
 int dfu3d_stk_global_index(const int32_t *idx, const uint8_t *empty, int64_t M, int32_t nsample, int64_t N,
@@ -115,7 +116,8 @@ int dfu3d_stk_global_index(const int32_t *idx, const uint8_t *empty, int64_t M, 
  *     x0 = floor(fx), x1 = x0 + 1, both clamped to [0, W - 1]; y0, y1 likewise in [0, H - 1];
  *     wa = (x1 - fx) * (y1 - fy), wb = (x1 - fx) * (fy - y0), wc = (fx - x0) * (y1 - fy), wd = (fx - x0) * (fy - y0)
  *     out = I[y0, x0] * wa + I[y1, x0] * wb + I[y0, x1] * wc + I[y1, x1] * wd, summed left to right.
- * A sample index outside [0, B) sets DFU3D_STK_ST_BAD_BATCH and the row is zeros; a non-finite fx or fy takes corner 0.
+ * A sample index outside [0, B) sets DFU3D_STK_ST_BAD_BATCH and the row is zeros; a non-finite fx (NaN, +inf, -inf)
+ * takes x0 = x1 = 0 and a non-finite fy y0 = y1 = 0, as the reference's floor().long() and clamp give on the host.
  * M >= 1, C, H, W >= 1, kstride >= 3, else DFU3D_EINVAL. */
 int dfu3d_stk_bev_sample(const float *keypoints, int32_t kstride, int64_t M, const float *spatial, int32_t B, int32_t C,
                          int32_t H, int32_t W, float range_x, float range_y, float voxel_x, float voxel_y,

@@ -180,8 +180,9 @@ __global__ __launch_bounds__(NT) void k_stk_fps(const float *__restrict__ xyz, i
 }
 
 __global__ __launch_bounds__(FPS_BIG_NT) void k_stk_fps_big(const float *__restrict__ xyz, int stride, int rows,
-                                                            const int *__restrict__ start, int K, int *idx, float *kp,
-                                                            float *__restrict__ tmp, uint32_t *__restrict__ status) {
+                                                            const int *__restrict__ start, int K, int bound, int *idx,
+                                                            float *kp, float *__restrict__ tmp,
+                                                            uint32_t *__restrict__ status) {
   constexpr int NW = FPS_BIG_NT / 64;
   __shared__ int4 s_a[2][NW];
   __shared__ float s_z[2][NW];
@@ -189,6 +190,10 @@ __global__ __launch_bounds__(FPS_BIG_NT) void k_stk_fps_big(const float *__restr
   uint32_t st = 0u;
   int lo0, n;
   sample_rows(start, b, rows, lo0, n, st);
+  if (n > bound) {                                   // as the register form: the rows beyond the bound are not looked at
+    st |= DFU3D_STK_ST_BAD_COUNT;
+    n = bound;
+  }
   if (n == 0) st |= DFU3D_STK_ST_EMPTY;
   const size_t out0 = (size_t)b * K;
   const int npick = n < K ? n : K;
@@ -319,10 +324,10 @@ __global__ __launch_bounds__(BT) void k_stk_gidx(const int *__restrict__ idx, co
   if (e < E) {
     const int m = (int)(e / ns);
     int g = -1;
+    const int b = sample_of(cstart, B, m);           // as k_stk_group: the starts are checked for an empty ball too
+    int lo = 0, n = 0;
+    if (b < B && cstart[b] <= m) sample_rows(start, b, N, lo, n, st); else st |= DFU3D_STK_ST_BAD_COUNT;
     if (!empty[m]) {
-      const int b = sample_of(cstart, B, m);
-      int lo = 0, n = 0;
-      if (b < B && cstart[b] <= m) sample_rows(start, b, N, lo, n, st); else st |= DFU3D_STK_ST_BAD_COUNT;
       const int i = idx[e];
       if ((unsigned)i < (unsigned)n) g = lo + i; else st |= DFU3D_STK_ST_BAD_INDEX;
     }
@@ -332,8 +337,11 @@ __global__ __launch_bounds__(BT) void k_stk_gidx(const int *__restrict__ idx, co
 }
 
 // ---- bilinear BEV sampling --------------------------------------------------------------------------------------------
-// floor(f) as the reference's .long() then clamp(0, hi) does it, and the same for floor(f) + 1; NaN -> 0
-__device__ __forceinline__ int clamp_floor(float fl, int hi) { return fl >= (float)hi ? hi : (fl >= 0.0f ? (int)fl : 0); }
+// floor(f) as the reference's .long() then clamp(0, hi) does it, and the same for floor(f) + 1; NaN and both
+// infinities -> 0 (.long() of a non-finite float is the most negative integer on the host): both compares are false
+__device__ __forceinline__ int clamp_floor(float fl, int hi) {
+  return fl >= 0.0f && fl <= 3.402823466e38f ? (fl >= (float)hi ? hi : (int)fl) : 0;
+}
 
 __global__ __launch_bounds__(BT) void k_stk_bev(const float *__restrict__ kp, int kstride, long long total,
                                                 const float *__restrict__ spatial, int B, int C, int H, int W, float rx,
@@ -437,7 +445,7 @@ extern "C" int dfu3d_stk_fps(const float *xyz, int32_t stride, int64_t rows, con
   else if (bound <= 8192) launch_fps<1024, 8>(xyz, stride, N, start, B, K, bound, idx, keypoints, status, st);
   else if (bound <= DFU3D_STK_FPS_ONCHIP) launch_fps<1024, 16>(xyz, stride, N, start, B, K, bound, idx, keypoints, status, st);
   else
-    hipLaunchKernelGGL(k_stk_fps_big, dim3(B), dim3(FPS_BIG_NT), 0, st, xyz, stride, N, start, K, idx, keypoints,
+    hipLaunchKernelGGL(k_stk_fps_big, dim3(B), dim3(FPS_BIG_NT), 0, st, xyz, stride, N, start, K, bound, idx, keypoints,
                        (float *)scratch, status);
   DFU3D_LAUNCH_CHECK();
   return DFU3D_OK;
@@ -450,9 +458,11 @@ extern "C" int dfu3d_stk_ball_query(const float *xyz, int32_t stride, int64_t N,
                                     int32_t nsample1, int32_t *idx1, uint8_t *empty1, uint32_t *status, void *stream) {
   DFU3D_CLEAR_STALE_ERROR();
   if (!status || B < 1 || n_scales < 1 || n_scales > DFU3D_STK_MAX_SCALES) return DFU3D_EINVAL;
-  if (!idx0 || !empty0 || nsample0 < 1 || radius0 != radius0) return DFU3D_EINVAL;
-  if (n_scales > 1 && (!idx1 || !empty1 || nsample1 < 1 || radius1 != radius1 || idx1 == idx0 || empty1 == empty0))
-    return DFU3D_EINVAL;
+  if (nsample0 < 1 || radius0 != radius0 || (n_scales > 1 && (nsample1 < 1 || radius1 != radius1))) return DFU3D_EINVAL;
+  if (M > 0) {                                       // without centres the outputs have no element: any pointer, NULL too
+    if (!idx0 || !empty0) return DFU3D_EINVAL;
+    if (n_scales > 1 && (!idx1 || !empty1 || idx1 == idx0 || empty1 == empty0)) return DFU3D_EINVAL;
+  }
   int rc = set_ok(xyz, stride, N, start, 3);
   if (rc == DFU3D_OK) rc = set_ok(centres, cstride, M, cstart, 3);
   if (rc != DFU3D_OK) return rc;

@@ -54,22 +54,19 @@ G26_ROIS = 6
 def sqdist(a, b):
     """(a.x-b.x)*(a.x-b.x) + (a.y-b.y)*(a.y-b.y) + (a.z-b.z)*(a.z-b.z), float32, left to right."""
     a, b = np.asarray(a, F32), np.asarray(b, F32)
-    dx, dy, dz = a[..., 0] - b[..., 0], a[..., 1] - b[..., 1], a[..., 2] - b[..., 2]
     with np.errstate(all='ignore'):
+        dx, dy, dz = a[..., 0] - b[..., 0], a[..., 1] - b[..., 1], a[..., 2] - b[..., 2]
         return (dx * dx + dy * dy) + dz * dz
 
 
 def counts(column, B):
     """column (rows,) float32 or int32 -> cnt int32 (B), start int32 (B + 1), status bits."""
     column = np.asarray(column)
-    cnt, st = np.zeros(B, np.int32), 0
-    for r, v in enumerate(column):
-        if 0 <= v < B and int(v) == v:
-            cnt[int(v)] += 1
-        else:
-            st |= ST_BAD_BATCH
-        if r + 1 < len(column) and column[r + 1] < v:
-            st |= ST_UNSORTED
+    with np.errstate(invalid='ignore'):
+        good = (column >= 0) & (column < B) & (np.floor(column) == column)      # all False for a NaN
+        unsorted = bool((column[1:] < column[:-1]).any())
+    cnt = np.bincount(column[good].astype(np.int64), minlength=B).astype(np.int32)
+    st = (0 if good.all() else ST_BAD_BATCH) | (ST_UNSORTED if unsorted else 0)
     return cnt, starts(cnt), st
 
 
@@ -79,9 +76,23 @@ def starts(cnt):
     return out
 
 
-def fps_one(xyz, npoint):
+def starts_status(cnt):
+    """The status of starts(): a negative count is taken as 0 and sets ST_BAD_COUNT."""
+    return ST_BAD_COUNT if (np.asarray(cnt, np.int64) < 0).any() else 0
+
+
+def sample_rows(start, b, rows):
+    """The rows of sample b inside [0, rows] -> lo, n, status: start[b] clamped to [0, rows], start[b + 1] to [lo, rows];
+    ST_BAD_COUNT when either moved."""
+    a, e = int(start[b]), int(start[b + 1])
+    lo = min(max(a, 0), rows)
+    hi = lo if e < lo else min(e, rows)
+    return lo, hi - lo, (ST_BAD_COUNT if (lo != a or hi != e) else 0)
+
+
+def fps_one(xyz, npoint, ties=None):
     """xyz (n, 3), n >= 1 -> int32 (npoint <= n): first pick 0, running minimum from 1e10, then the largest running minimum,
-    the lowest index among equals."""
+    the lowest index among equals.  ties: a list that receives every step with more than one candidate at the maximum."""
     xyz = np.asarray(xyz, F32)
     idx = np.zeros(npoint, np.int32)
     run = np.full(len(xyz), 1e10, F32)
@@ -91,22 +102,53 @@ def fps_one(xyz, npoint):
         with np.errstate(invalid='ignore'):
             run = np.where(d < run, d, run)
         old = int(np.argmax(run))
+        if ties is not None and int((run == run[old]).sum()) > 1:
+            ties.append(s)
         idx[s] = old
     return idx
 
 
-def fps(xyz, start, K):
+def fps_plain64(xyz, npoint):
+    """The same sampling in float64, written without the restatement's helpers: on coordinates whose differences, squares
+    and sums are exact in float32 it is the restatement's picks index for index."""
+    p = np.asarray(xyz, np.float64)
+    run = np.full(len(p), 1e10)
+    picks = [0]
+    for _ in range(1, npoint):
+        q = p[picks[-1]]
+        run = np.minimum(run, ((p - q) ** 2).sum(axis=1))
+        picks.append(int(np.flatnonzero(run == run.max())[0]))
+    return np.asarray(picks, np.int32)
+
+
+def fps_bound(rows, cap):
+    """The bound on a sample: cap if 1 <= cap < rows, else rows."""
+    return cap if 1 <= cap < rows else rows
+
+
+def fps(xyz, start, K, cap=0, rows=None):
     """xyz (N, 3) stacked -> idx int32 (B, K) sample-local, keypoints (B * K, 4), status.  A short sample cycles its picks;
-    an empty one writes index 0, a zero keypoint and ST_EMPTY."""
+    an empty one writes index 0, a zero keypoint and ST_EMPTY.  rows: the rows the call is told of (default: all of xyz);
+    starts are clamped as sample_rows states.  A sample beyond fps_bound(rows, cap) is cut to its first `bound` rows and
+    sets ST_BAD_COUNT.  A non-finite coordinate among the sampled rows sets ST_BAD_POINT: the picks returned for that
+    sample are then NOT specified (only that they lie inside the sample)."""
     xyz = np.asarray(xyz, F32)
+    rows = len(xyz) if rows is None else int(rows)
+    bound = fps_bound(rows, int(cap))
     B = len(start) - 1
     idx, kp, st = np.zeros((B, K), np.int32), np.zeros((B * K, 4), F32), 0
     for b in range(B):
-        lo, n = int(start[b]), int(start[b + 1] - start[b])
+        lo, n, bad = sample_rows(start, b, rows)
+        st |= bad
+        if n > bound:
+            st |= ST_BAD_COUNT
+            n = bound
         kp[b * K:(b + 1) * K, 0] = b
         if n == 0:
             st |= ST_EMPTY
             continue
+        if not np.isfinite(xyz[lo:lo + n]).all():
+            st |= ST_BAD_POINT
         picks = fps_one(xyz[lo:lo + n], min(n, K))
         for j in range(K):
             idx[b, j] = picks[j % len(picks)]
@@ -121,84 +163,155 @@ def sample_of(start, m):
     return -1
 
 
-def ball_query(xyz, start, centres, cstart, radius, nsample):
+def centre_rows(start, cstart, m, N):
+    """The rows of the sample of centre m -> lo, n, status: sample_rows of the sample whose centres hold m; a centre at or
+    beyond cstart[B] has no sample: no rows and ST_BAD_COUNT."""
+    b = sample_of(cstart, m)
+    return (0, 0, ST_BAD_COUNT) if b < 0 else sample_rows(start, b, N)
+
+
+def ball_query(xyz, start, centres, cstart, radius, nsample, with_status=False):
     """-> idx int32 (M, nsample) sample-local: the first nsample indices, ascending, with d2 < radius * radius (strict,
-    float32) among the centre's own sample; the rest the first hit; zeros and empty = 1 without one."""
+    float32) among the centre's own sample; the rest the first hit; zeros and empty = 1 without one.  Starts are clamped
+    to the rows of xyz as sample_rows states; a centre beyond cstart[B] is an empty ball and sets ST_BAD_COUNT.
+    with_status: the status bits as a third result."""
     xyz, centres = np.asarray(xyz, F32).reshape(-1, 3), np.asarray(centres, F32).reshape(-1, 3)
     M = len(centres)
     r2 = F32(radius) * F32(radius)
-    idx, empty = np.zeros((M, nsample), np.int32), np.ones(M, np.uint8)
+    idx, empty, st = np.zeros((M, nsample), np.int32), np.ones(M, np.uint8), 0
     for m in range(M):
-        b = sample_of(cstart, m)
-        if b < 0:
-            continue
-        lo, hi = int(start[b]), int(start[b + 1])
+        lo, n, bad = centre_rows(start, cstart, m, len(xyz))
+        st |= bad
         with np.errstate(invalid='ignore'):
-            hits = np.nonzero(sqdist(centres[m], xyz[lo:hi]) < r2)[0][:nsample]   # the walk stops at nsample hits
+            hits = np.nonzero(sqdist(centres[m], xyz[lo:lo + n]) < r2)[0][:nsample]   # the walk stops at nsample hits
         if len(hits):
             idx[m, :] = hits[0]
             idx[m, :len(hits)] = hits
             empty[m] = 0
-    return idx, empty
+    return (idx, empty, st) if with_status else (idx, empty)
 
 
-def group(xyz, start, centres, cstart, features, idx, empty):
-    """-> (3 + C, M, nsample): xyz[start_b + idx] - centre, then the feature row (bits); empty balls zeros."""
-    xyz, centres = np.asarray(xyz, F32).reshape(-1, 3), np.asarray(centres, F32).reshape(-1, 3)
+def group(xyz, start, centres, cstart, features, idx, empty, with_status=False):
+    """-> (3 + C, M, nsample): xyz[start_b + idx] - centre, then the feature row (bits); empty balls zeros.  xyz and
+    centres None: the plain form, (C, M, nsample).  Starts are clamped (over the rows of xyz, or of the features in the
+    plain form); a centre beyond cstart[B] sets ST_BAD_COUNT; an index outside its sample (of a ball not marked empty) sets
+    ST_BAD_INDEX and reads row 0 of the sample, zeros for a sample without rows."""
+    plain = xyz is None
+    if not plain:
+        xyz, centres = np.asarray(xyz, F32).reshape(-1, 3), np.asarray(centres, F32).reshape(-1, 3)
     M, ns = idx.shape
     C = 0 if features is None else features.shape[1]
-    out = np.zeros((3 + C, M, ns), F32)
+    N = len(features) if plain else len(xyz)
+    xo = 0 if plain else 3
+    out, st = np.zeros((xo + C, M, ns), F32), 0
     bits = out.view(np.uint32)
     for m in range(M):
+        lo, n, bad = centre_rows(start, cstart, m, N)
+        st |= bad
         if empty[m]:
             continue
-        lo = int(start[sample_of(cstart, m)])
         for j in range(ns):
-            g = lo + int(idx[m, j])
-            out[0:3, m, j] = xyz[g] - centres[m]
+            i = int(idx[m, j])
+            if not 0 <= i < n:
+                st |= ST_BAD_INDEX
+                i = 0
+                if n == 0:
+                    continue
+            g = lo + i
+            if not plain:
+                out[0:3, m, j] = xyz[g] - centres[m]
             if C:
-                bits[3:, m, j] = features[g].view(np.uint32)
-    return out
+                bits[xo:, m, j] = features[g].view(np.uint32)
+    return (out, st) if with_status else out
 
 
-def group_backward(grad_out, start, cstart, idx, empty, N):
-    """grad_out (3 + C, M, nsample) -> (N, C): per source row the entries in ascending entry number, one float32 addition
-    each, from +0.0."""
-    C, (M, ns) = grad_out.shape[0] - 3, idx.shape
-    gf = np.zeros((N, C), F32)
+def global_index(start, cstart, idx, empty, N):
+    """-> gidx int32 (M * nsample), status: start_b + idx, -1 for the entries of an empty ball and for an index outside its
+    sample (ST_BAD_INDEX); a centre beyond cstart[B] sets ST_BAD_COUNT, whether its ball is marked empty or not."""
+    M, ns = idx.shape
+    gidx, st = np.full((M, ns), -1, np.int32), 0
     for m in range(M):
+        lo, n, bad = centre_rows(start, cstart, m, N)
+        st |= bad
         if empty[m]:
             continue
-        lo = int(start[sample_of(cstart, m)])
         for j in range(ns):
-            g = lo + int(idx[m, j])
-            gf[g] = gf[g] + grad_out[3:, m, j]
-    return gf
+            i = int(idx[m, j])
+            if 0 <= i < n:
+                gidx[m, j] = lo + i
+            else:
+                st |= ST_BAD_INDEX
+    return gidx.reshape(-1), st
 
 
-def bev_sample(keypoints, spatial, pc_range, voxel_size, bev_stride):
-    """keypoints (M, 4), spatial (B, C, H, W) -> (M, C); the reference's arithmetic in float32."""
+def group_backward(grad_out, start, cstart, idx, empty, N, with_status=False, skip=3):
+    """grad_out (skip + C, M, nsample) -> (N, C): per source row the entries in ascending entry number, one float32
+    addition each, from +0.0; the entries global_index marks -1 are left out."""
+    C, (M, ns) = grad_out.shape[0] - skip, idx.shape
+    gidx, st = global_index(start, cstart, idx, empty, N)
+    gf = np.zeros((N, C), F32)
+    flat = grad_out[skip:].reshape(C, M * ns)
+    for e in np.flatnonzero(gidx >= 0):
+        gf[gidx[e]] = gf[gidx[e]] + flat[:, e]
+    return (gf, st) if with_status else gf
+
+
+def clamp_floor(f, hi):
+    """floor(f) (an integral float) clamped to [0, hi]; NaN and both infinities give 0, as the reference's
+    torch.floor(x).long() followed by torch.clamp(x0, 0, hi) does on the host, where the conversion of a non-finite float
+    is the most negative int64 -- and so is that value + 1."""
+    if not np.isfinite(f):
+        return 0
+    return int(min(max(f, F32(0.0)), F32(hi)))
+
+
+def bev_sample(keypoints, spatial, pc_range, voxel_size, bev_stride, with_status=False):
+    """keypoints (M, 4), spatial (B, C, H, W) -> (M, C); the reference's arithmetic in float32.  A sample index outside
+    [0, B) or not an integer: a row of zeros and ST_BAD_BATCH.  A non-finite map coordinate takes index 0 on its axis for
+    both neighbours (clamp_floor)."""
     kp, sp = np.asarray(keypoints, F32), np.asarray(spatial, F32)
     B, C, H, W = sp.shape
-    out = np.zeros((len(kp), C), F32)
+    out, st = np.zeros((len(kp), C), F32), 0
     with np.errstate(all='ignore'):
         fx = ((kp[:, 1] - F32(pc_range[0])) / F32(voxel_size[0])) / F32(bev_stride)
         fy = ((kp[:, 2] - F32(pc_range[1])) / F32(voxel_size[1])) / F32(bev_stride)
-    for m in range(len(kp)):
-        b = int(kp[m, 0])
-        x, y = fx[m], fy[m]
-        x0 = int(np.floor(x))
-        y0 = int(np.floor(y))
-        x1, y1 = x0 + 1, y0 + 1
-        x0, x1 = min(max(x0, 0), W - 1), min(max(x1, 0), W - 1)
-        y0, y1 = min(max(y0, 0), H - 1), min(max(y1, 0), H - 1)
-        Ia, Ib, Ic, Id = sp[b, :, y0, x0], sp[b, :, y1, x0], sp[b, :, y0, x1], sp[b, :, y1, x1]
-        wa = (F32(x1) - x) * (F32(y1) - y)
-        wb = (F32(x1) - x) * (y - F32(y0))
-        wc = (x - F32(x0)) * (F32(y1) - y)
-        wd = (x - F32(x0)) * (y - F32(y0))
-        out[m] = ((Ia * wa + Ib * wb) + Ic * wc) + Id * wd
-    return out
+        for m in range(len(kp)):
+            fb = kp[m, 0]
+            if not (fb >= 0 and fb < B and np.floor(fb) == fb):
+                st |= ST_BAD_BATCH
+                continue
+            b = int(fb)
+            x, y = fx[m], fy[m]
+            flx, fly = np.floor(x), np.floor(y)
+            x0, x1 = clamp_floor(flx, W - 1), clamp_floor(flx + F32(1.0), W - 1)
+            y0, y1 = clamp_floor(fly, H - 1), clamp_floor(fly + F32(1.0), H - 1)
+            Ia, Ib, Ic, Id = sp[b, :, y0, x0], sp[b, :, y1, x0], sp[b, :, y0, x1], sp[b, :, y1, x1]
+            wa = (F32(x1) - x) * (F32(y1) - y)
+            wb = (F32(x1) - x) * (y - F32(y0))
+            wc = (x - F32(x0)) * (F32(y1) - y)
+            wd = (x - F32(x0)) * (y - F32(y0))
+            out[m] = ((Ia * wa + Ib * wb) + Ic * wc) + Id * wd
+    return (out, st) if with_status else out
+
+
+def same_bits_or_nan(a, b):
+    """Bit equality, except that any NaN equals any NaN: IEEE 754 leaves the sign and payload of the NaN an invalid
+    operation (inf - inf, 0 * inf) makes to the implementation, and a processor and NumPy differ in them."""
+    a, b = np.ascontiguousarray(a, F32), np.ascontiguousarray(b, F32)
+    if a.shape != b.shape:
+        return False
+    na, nb = np.isnan(a), np.isnan(b)
+    return bool((na == nb).all() and np.array_equal(a.view(np.uint32)[~na], b.view(np.uint32)[~nb]))
+
+
+def lattice_cloud(seed, counts_, pitch=0.25, span=2):
+    """rows of all samples, float32 (sum, 3), and its start array: integer multiples of `pitch` in [-span, span] * pitch on
+    every axis, so that with a pitch that is a power of two and a small span every float32 subtraction, square and sum of a
+    squared distance is exact (pitch 0.25, span 2: multiples of 1/16 up to 3).  (2 * span + 1) ** 3 cells: a sample with
+    more rows than that has duplicates, and the maxima of farthest point sampling tie."""
+    n = int(sum(counts_))
+    cells = np.random.default_rng(seed).integers(-span, span + 1, (n, 3))
+    return (cells * pitch).astype(F32), starts(counts_)
 
 
 def stacked_cloud(seed, counts_, scale=2.0):

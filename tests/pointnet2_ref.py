@@ -7,6 +7,11 @@ F32 = np.float32
 
 # (B, N, npoint): farthest point sampling
 FPS_CASES = [(1, 1, 1), (2, 63, 63), (3, 1000, 37), (2, 1025, 256)]
+# the register shapes of dfu3d_pn2_fps no case above launches: <1024,2> (2049 > 2048 takes <1024,4>), <1024,4> at its upper
+# edge, <1024,8> on both of its edges
+FPS_SHAPE_CASES = [(2, 2049, 64), (2, 4096, 64), (2, 4097, 64), (2, 8192, 64)]
+# N per kernel of the dispatch ladder, for the lattice cloud: <256,1>, <256,4>, <1024,2>, <1024,4>, <1024,8>, <1024,16>, big
+FPS_LATTICE_N = [200, 1000, 2000, 4000, 8000, 16000, 17000]
 FPS_LEVEL1 = (2, 16384, 4096)                # the configuration's first level
 FPS_BIG = (1, 16384 + 1000, 96)              # above DFU3D_PN2_FPS_ONCHIP: the form with the minima in the scratch
 BALL_N = [1, 64, 65, 1000]
@@ -36,6 +41,12 @@ FULL_INPUT_CHANNELS = 4
 def cloud(seed, B, N, scale=4.0):
     """(B, N, 3) float32 from a continuous distribution."""
     return (np.random.default_rng(seed).normal(0.0, 1.0, (B, N, 3)) * scale).astype(F32)
+
+
+def lattice_cloud(seed, B, N, pitch=0.25, span=2):
+    """(B, N, 3) float32 on a lattice: integer multiples of `pitch` in [-span, span] * pitch, so every float32 operation of
+    a squared distance is exact, points repeat ((2 * span + 1) ** 3 cells) and the maxima of farthest point sampling tie."""
+    return (np.random.default_rng(seed).integers(-span, span + 1, (B, N, 3)) * pitch).astype(F32)
 
 
 def sqdist(a, b):

@@ -32,6 +32,10 @@ Entry points run, per family (every one of them could be driven under the mode):
   pointnet2     fps (N = 700 and FPS_BIG: both sides of FPS_ONCHIP), ball_query (BALL_N x BALL_M, one and two scales per
                 launch), group (C = 0 too), three_nn (m < 3 too), three_interpolate, invert / inverse_of, gather_backward
                 through grouping, query_group and interpolate on BWD_CASES.
+  point_stack   in tests/test_gpu_point_stack_edges.py, one family per test: counts (float and int columns) and starts; fps at
+                300, 5000 and [16500, 90] rows (both sides of FPS_ONCHIP: the memory form's scratch arrives poisoned);
+                ball_query on grid_case (two scales per launch, and one); group (C = 0, C = 17, the plain form);
+                query_group through .backward(); bev_sample.
   roipoint      pool and pool_fused on every case of tests/roipoint_ref.py, and feature rows off 16 bytes.
   rcnn_target   point_targets, roi_max_iou (by class and not), roi_subsample on every shape of their test.
   proposals     proposal_ops.proposals: N = 1, 63, 64, 65, 129, 200 and 2500 candidates of 3000.

@@ -36,7 +36,7 @@ def run_fps(xyz, npoint):
 
 
 # ---- farthest point sampling -------------------------------------------------------------------------------------------
-@pytest.mark.parametrize("case", R.FPS_CASES + [R.FPS_LEVEL1, R.FPS_BIG], ids=str)
+@pytest.mark.parametrize("case", R.FPS_CASES + R.FPS_SHAPE_CASES + [R.FPS_LEVEL1, R.FPS_BIG], ids=str)
 def test_fps_matches_the_restatement(case):
     from dfu3d_amd import pointnet2_ops as ops
     B, N, npoint = case
@@ -65,6 +65,21 @@ def test_fps_ties_take_the_lowest_index(N):
     i2, x2, _ = run_fps(twice, 40)
     assert np.array_equal(x1, x2) and np.array_equal(i2, 2 * i1)
     assert np.array_equal(i1, R.fps(half, 40)[0]) and np.array_equal(i2, R.fps(twice, 40)[0])
+
+
+@pytest.mark.parametrize("N", R.FPS_LATTICE_N)
+def test_fps_lattice_cloud_ties_in_every_kernel_shape(N):
+    """A cloud on a 0.25 lattice with every cell taken many times: steps whose maxima tie across the points of a thread,
+    the lanes of a wave and the waves of the workgroup, in each of the seven kernels of the dispatch ladder."""
+    from dfu3d_amd import pointnet2_ops as ops
+    assert (N > ops.FPS_ONCHIP) == (N == R.FPS_LATTICE_N[-1])
+    xyz = R.lattice_cloud(2100 + N, 2, N)
+    ties = []
+    want_idx, want_xyz = R.fps(xyz, 64, ties)
+    assert {b for b, _ in ties} == {0, 1}                                  # otherwise the lattice proves nothing
+    idx, new_xyz, st = run_fps(xyz, 64)
+    assert st == 0 and np.array_equal(idx, want_idx)
+    assert np.array_equal(new_xyz.view(np.uint32), want_xyz.view(np.uint32))
 
 
 @pytest.mark.parametrize("N", [300, R.FPS_BIG[1]])

@@ -125,6 +125,17 @@ def test_bad_arguments_return_before_any_launch():
     assert sb(40000, 16385) == 40000 * 4
 
 
+def test_ball_query_without_centres_needs_no_outputs():
+    """M = 0: the outputs have no element, so the pointers torch gives for them are NULL; the call is a no-op, not
+    DFU3D_EINVAL.  What does not depend on M is still checked."""
+    L = _lib_stk.lib()
+    OK, EINVAL = _lib.CONSTANTS["DFU3D_OK"], _lib.CONSTANTS["DFU3D_EINVAL"]
+    none = dict(M=0, ctr=None, i0=None, e0=None, i1=None, e1=None)
+    assert _ball(L, **none) == OK and _ball(L, S=1, **none) == OK
+    assert _ball(L, n1=0, **none) == EINVAL and _ball(L, r0=float('nan'), **none) == EINVAL
+    assert _ball(L, cstart=None, **none) == EINVAL and _ball(L, status=None, **none) == EINVAL
+
+
 def test_ops_refuse_host_wrong_type_and_non_contiguous_tensors():
     import torch
     from dfu3d_amd import point_stack_ops as ops
