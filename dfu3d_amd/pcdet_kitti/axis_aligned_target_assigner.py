@@ -58,11 +58,16 @@ class AxisAlignedTargetAssigner(object):
 
     def flat_anchors(self, all_anchors):
         """torch.cat(all_anchors, dim=-3) as (A, 7): y, x, then the classes one after another.  Kept for the next call
-        with the same tensors."""
-        key = tuple((a.data_ptr(), tuple(a.shape), a.device) for a in all_anchors)
-        if self._flat is None or self._flat[0] != key:
-            self._flat = (key, torch.cat(list(all_anchors), dim=-3).view(-1, 7).contiguous())
-        return self._flat[1]
+        with the same tensors, unchanged: the source tensors are held here (an address alone comes back from the
+        allocator under other values) and compared by identity and by their version counter, which every in-place
+        write moves."""
+        src = list(all_anchors)
+        versions = [a._version for a in src]
+        kept = self._flat
+        if (kept is None or len(kept[0]) != len(src) or any(a is not b for a, b in zip(kept[0], src))
+                or kept[1] != versions):
+            self._flat = (src, versions, torch.cat(src, dim=-3).view(-1, 7).contiguous())
+        return self._flat[2]
 
     def assign_targets(self, all_anchors, gt_boxes_with_classes):
         """all_anchors: [(nz, ny, nx, #size, #rot, 7), ...] per anchor class; gt_boxes_with_classes (B, M, 8) ->

@@ -1,6 +1,8 @@
 """The anchor target stage and the SECOND detector without a GPU: the agreement of csrc/dfu3d_anc.h with its binding,
 host-side argument validation before any launch, the restatement (tests/anchor_target_ref.py) and AnchorGenerator against
-the reference's recorded run (golden G25) bit for bit, the cases of the GPU test checked with the restatement, the head's
+the reference's recorded run (golden G25) bit for bit, the cases of the GPU tests checked with the restatement, the
+restatement's class sets on a flat block against its per-class form and against golden G27 (the reference's assigner at
+uneven sets), the assigner's kept flat block after its source tensors changed, the head's
 losses and decoding on the golden's predictions and targets (plain torch: they run on the CPU as well), SECONDNet's
 state-dict keys, and the settings that raise."""
 import ctypes
@@ -22,6 +24,7 @@ POINTERS = ('anchors', 'set_begin', 'matched', 'unmatched', 'class_id', 'gt_boxe
 HOST = ('set_begin', 'matched', 'unmatched', 'class_id')        # read on the host during the call
 HERE = os.path.dirname(os.path.abspath(__file__))
 GOLDEN = os.path.join(HERE, "golden", "g25_anchor_head.npz")
+G27 = os.path.join(HERE, "golden", "g27_anchor_assigner.npz")
 G24 = os.path.join(HERE, "golden", "g24_spconv_backbone_keys.json")
 
 
@@ -179,6 +182,147 @@ def test_the_restatement_equals_the_reference(golden):
 def test_the_cases_of_the_gpu_test_hold_their_conditions():
     res = R.check_cases()
     assert len(res) == 10 and all(lab.shape == (1, 13260) for lab, _, _ in res.values())
+
+
+def test_assign_flat_equals_assign_targets(golden):
+    """The class sets on a flat block (any extents) against the concatenation along the sizes axis, on G25's layout and on
+    the layout of the cases: the same bits."""
+    g, _ = golden
+    anchors, _ = R.generate_anchors(R.G25_RANGE, R.feature_map_sizes(R.G25_GRID))
+    pairs = [(anchors, g['gt_boxes'])]
+    anchors = R.case_anchors()
+    cs = R.cases()
+    pairs.append((anchors, np.stack([cs[n] for n in cs])))
+    for all_anchors, gt in pairs:
+        want = R.assign_targets(all_anchors, gt)
+        got = R.assign_flat_rows(R.flat(all_anchors), R.class_sets(all_anchors), gt)
+        assert (want[0] > 0).any() and (want[0] == -1).any()
+        assert all(u.dtype == v.dtype and u.tobytes() == v.tobytes() for u, v in zip(got[:3], want))
+        assert np.array_equal(got[3], R.foreground_rows(all_anchors, gt))
+        assert np.array_equal(R.foreground_rows_flat(R.flat(all_anchors), R.class_sets(all_anchors), gt), got[3])
+
+
+def test_the_edge_cases_hold_their_conditions():
+    res = R.check_edge_cases()
+    assert list(res) == R.EDGE_NAMES and len(res) == 18
+    assert sorted({c['flat'].shape[0] for c, _ in res.values()}) == [6, 126, 252, 504, 756, 768, 1536]
+    assert {len(c['sets']) for c, _ in res.values()} == {1, 3, 8}
+    big = R.check_big_m_cases()
+    assert [g.shape[1] for g, _ in big.values()] == [512, 512, 257] and list(big) == R.BIG_M_NAMES
+    assert all(w[0].shape == (1, 13260) for _, w in big.values())
+    case, want = R.batch_limit_case()
+    K = _lib_anc.CONSTANTS
+    assert case['gt'].shape == (K['DFU3D_ANC_MAX_BATCH'], 1, 8) and want[1].shape == (65535, 6, 7) and (want[0][-1] > 0).any()
+
+
+def test_the_restatement_equals_golden_g27():
+    """The reference's assigner alone, five class names, anchor classes (3, 1, 5) with 3, 6 and 3 slots: every bit, through
+    assign_targets and through assign_flat; and the fixture holds the conditions it was built for."""
+    g = np.load(G27)
+    meta = json.loads(bytes(g['meta']).decode())
+    cfg27, names = R.G27_ANCHOR_CFG, R.G27_CLASS_NAMES
+    assert meta['classes'] == names and meta['num_anchors_per_location'] == [3, 6, 3] and os.path.getsize(G27) <= os.path.getsize(GOLDEN)
+    anchors, per_loc = R.generate_anchors(R.G27_RANGE, R.feature_map_sizes(R.G27_GRID, cfg27), cfg27)
+    assert per_loc == [3, 6, 3] and [a.shape for a in anchors] == [(1, 17, 17, 1, 3, 7), (1, 17, 17, 2, 3, 7), (1, 17, 17, 1, 3, 7)]
+    assert all(np.array_equal(bits(a), bits(g['anchors%d' % k])) for k, a in enumerate(anchors))
+    assert np.array_equal(bits(R.flat(anchors)), bits(g['anchors']))
+    gt = g['gt_boxes']
+    assert np.array_equal(bits(gt), bits(R.g27_boxes())) and gt.shape == (R.G27_B, R.G27_M, 8)
+    sets = R.class_sets(anchors, cfg27, names)
+    assert sets == [(3, 0.5, 0.5, 3), (6, 0.5, 0.25, 1), (3, 0.75, 0.25, 5)]
+    rec = []
+    flat_out = R.assign_flat_rows(R.flat(anchors), sets, gt, rec)
+    for got in (R.assign_targets(anchors, gt, cfg27, names), flat_out[:3]):
+        assert got[0].dtype == np.int32 and np.array_equal(got[0], g['box_cls_labels'])
+        assert np.array_equal(bits(got[2]), bits(g['reg_weights'])) and np.array_equal(bits(got[1]), bits(g['box_reg_targets']))
+    # sample 0, the Car set: anchors that no box forces exactly on matched (positive) and exactly on unmatched (-1)
+    r = rec[1]
+    loose = np.setdiff1d(np.arange(len(r['best'])), r['forced'])
+    assert any(r['best'][a] == 0.5 and r['labels'][a] == 1 for a in loose)
+    assert any(r['best'][a] == 0.25 and r['labels'][a] == -1 for a in loose)
+    # the Cyclist set has unmatched == matched: no -1 in any sample, and anchors on the shared value
+    assert all(not (rec[3 * b]['labels'] == -1).any() for b in range(3)) and (rec[0]['best'] == 0.5).any()
+    # sample 1: the rows of the classes 2 and 4 change nothing; a class-0 row forces an anchor to label 0 and wins an arg max
+    assert sorted(set(gt[1, :, 7].astype(int).tolist())) == [0, 1, 2, 3, 4, 5]
+    drop = [k for k in range(R.G27_M) if gt[1, k, 7] in (2, 4)]
+    less = np.zeros_like(gt[1:2])
+    keep = [k for k in range(R.G27_M) if k not in drop]
+    less[0, :len(keep)] = gt[1, keep]
+    assert len(drop) >= 3 and all(u.tobytes() == v[1:2].tobytes() for u, v in zip(R.assign_flat(R.flat(anchors), sets, less), flat_out[:3]))
+    r = rec[3 + 2]
+    zero = [k for k, row in enumerate(r['own']) if gt[1, row, 7] == 0 and gt[1, row, 3] > 0]
+    assert any(r['top'][k] > 0 and (r['labels'][np.nonzero(r['iou'][:, k] == r['top'][k])[0]] == 0).all() for k in zero)
+    truck = list(r['own']).index(3)
+    assert any(r['arg'][a] in zero and 0 < r['iou'][a, truck] < r['best'][a] and r['labels'][a] == 0 for a in range(len(r['best'])))
+    assert not gt[2, 9:].any() and not gt[1, 2].any() and (flat_out[0] > 0).any(1).all()
+
+
+# ---- the assigner's flattened block follows its source tensors -----------------------------------------------------------------
+FLAT_N = 3 * 10 * 12 * 2 * 7
+
+
+def flat_sum(x):
+    return float(x.double().sum())
+
+
+def fresh_anchors(value):
+    import torch
+    return [torch.full((1, 10, 12, 1, 2, 7), float(value)) for _ in range(3)]
+
+
+def new_assigner():
+    from dfu3d_amd.pcdet_kitti.axis_aligned_target_assigner import AxisAlignedTargetAssigner
+    from dfu3d_amd.pcdet_kitti.box_coder_utils import ResidualCoder
+    return AxisAlignedTargetAssigner(cfg(R.HEAD_CFG), R.CLASS_NAMES, ResidualCoder())
+
+
+def test_flat_anchors_after_an_in_place_change():
+    import torch
+    assigner, a = new_assigner(), fresh_anchors(1.0)
+    first = assigner.flat_anchors(a)
+    assert first.shape == (720, 7) and flat_sum(first) == FLAT_N
+    a[0].add_(1.0)
+    second = assigner.flat_anchors(a)
+    assert flat_sum(second) == FLAT_N + FLAT_N // 3 and torch.equal(second, torch.cat(a, dim=-3).view(-1, 7))
+    assert assigner.flat_anchors(a) is second
+    a[2][0, 3, 4, 0, 1, 5] = 9.0                                               # through a view: the version moves as well
+    assert flat_sum(assigner.flat_anchors(a)) == FLAT_N + FLAT_N // 3 + 8
+
+
+def test_flat_anchors_after_new_tensors_of_the_same_shape():
+    """The old tensors are dropped before the new ones are made, so the allocator may hand out the old addresses again."""
+    assigner = new_assigner()
+    for value in (1.0, 2.0, 3.0, 4.0):
+        a = fresh_anchors(value)
+        got = assigner.flat_anchors(a)
+        assert flat_sum(got) == value * FLAT_N, value
+        assert assigner.flat_anchors(a) is got
+        del a, got
+    a = fresh_anchors(5.0)
+    a[1] = a[1] + 1.0                                                           # one entry of the list replaced
+    assert flat_sum(assigner.flat_anchors(a)) == 5.0 * FLAT_N + FLAT_N // 3
+    # whether the allocator does so is its business; memory the test owns states it: new tensors, the old addresses
+    import torch
+    mem = np.ones((3, 1, 10, 12, 1, 2, 7), np.float32)
+    a = [torch.from_numpy(m) for m in mem]
+    where = [t.data_ptr() for t in a]
+    assert flat_sum(assigner.flat_anchors(a)) == FLAT_N
+    del a
+    mem *= 2.0
+    a = [torch.from_numpy(m) for m in mem]
+    assert [t.data_ptr() for t in a] == where and flat_sum(assigner.flat_anchors(a)) == 2.0 * FLAT_N
+
+
+def test_flat_anchors_unchanged_is_one_cat(monkeypatch):
+    import torch
+    from dfu3d_amd.pcdet_kitti import axis_aligned_target_assigner as mod
+    calls = []
+    real = torch.cat
+    monkeypatch.setattr(mod.torch, "cat", lambda *a, **k: (calls.append(1), real(*a, **k))[1])
+    assigner, a = new_assigner(), fresh_anchors(1.0)
+    first = assigner.flat_anchors(a)
+    assert all(assigner.flat_anchors(x) is first for x in (a, list(a), tuple(a), a)) and len(calls) == 1
+    assert first.is_contiguous() and first.shape == (720, 7) and all(t._version == 0 for t in a)
 
 
 def test_anchor_generator_equals_the_reference(golden):

@@ -45,8 +45,10 @@ def run(all_anchors, gt):
     return ops.assign_targets(cu(R.flat(all_anchors)), R.class_sets(all_anchors), cu(gt))
 
 
-def compare(name, got, want, all_anchors, gt):
-    """got: the stage's three tensors; want: the golden's or the restatement's three arrays."""
+def compare(name, got, want, all_anchors, gt, class_sets=None, flat=None, rows=None):
+    """got: the stage's three tensors; want: the golden's or the restatement's three arrays.  The anchors are all_anchors
+    (per class, the KITTI sets), or the block `flat` with its class_sets; rows: the restatement's foreground rows where the
+    caller has them already."""
     from dfu3d_amd.pcdet_kitti.box_coder_utils import ResidualCoder
     labels, targets, weights = (t.cpu().numpy() for t in got)
     assert labels.dtype == np.int32 and targets.dtype == np.float32 and weights.dtype == np.float32
@@ -57,9 +59,13 @@ def compare(name, got, want, all_anchors, gt):
     assert not bits(targets[~fg]).any(), name                          # exactly +0.0
     if not fg.any():
         return
-    rows = R.foreground_rows(all_anchors, gt)
+    if flat is None:
+        flat = R.flat(all_anchors)
+        rows = R.foreground_rows(all_anchors, gt) if rows is None else rows
+    elif rows is None:
+        rows = R.foreground_rows_flat(flat, class_sets, gt)
     b, a = np.nonzero(fg)
-    plain = ResidualCoder().encode_torch(cu(gt[b, rows[b, a], :7]), cu(R.flat(all_anchors)[a])).cpu().numpy()
+    plain = ResidualCoder().encode_torch(cu(gt[b, rows[b, a], :7]), cu(flat[a])).cpu().numpy()
     gold = want[1][fg]
     d_hip, d_torch = float(np.abs(targets[fg] - gold).max()), float(np.abs(plain - gold).max())
     floor = 4.0 * float(np.spacing(np.float32(np.abs(gold).max())))
